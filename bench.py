@@ -24,7 +24,15 @@ Synthetic Reddit-shaped graph: Chung-Lu lognormal sigma 1.3, N 
 `--cpu`: BASELINE config 1 (samp 512, batch 128, one process on the CPU through the product's
 torch.sparse.mm device branch).
 
-Run: python bench.py [--gpus N --steps K --warmup W]. For N > 1 the command starts its own N rank
+A plain run (no `--full`) does what the headline needs and nothing else: set-up, warm-up, the
+`--steps` timed end-to-end steps, the result line. `--full` adds every other measurement around
+it (the PMC traffic and site-trace child runs, `gpu_step` and the roofline over the distinct
+batches, the A/B passes, the drop-in timing, the sampler cost, the CPU baseline); the headline
+window is the same in both. `--dump-outputs DIR` writes what the last timed step handed back
+(the loss and the parameters it left) as DIR/<name>.npy, float32: graph, model, batches and
+dropout masks are seeded, so two builds run with the same arguments can be compared array by array.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full]. For N > 1 the command starts its own N rank
 processes (gnn_amd.launch, before any GPU call; as the reference's one `python main.py` starts a
 trainer per device, main.py:289-297) unless a launcher (torch.distributed.run) already set
 WORLD_SIZE. Rank 0 prints ONE JSON line.
@@ -66,11 +74,18 @@ SAMPLERS = {"ladies": sampler.ladies_sample_host, "subgraph": sampler.subgraph_s
             "fastgcn": sampler.fastgcn_sample_host}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the PMC traffic and site-trace child runs, gpu_step, the roofline, "
+                         "the A/B passes, the drop-in timing, the sampler cost and the CPU baseline (each can be "
+                         "switched off by its --no-... option); without --full none of them runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (loss.npy) and the "
+                         "parameters it left (param_NN_<name>.npy) into DIR as float32 arrays")
     ap.add_argument("--gpu-step-batches", type=int, default=60,
                     help="distinct pre-sampled batches timed for the gpu_step field (at most --steps)")
     ap.add_argument("--model", default="graphsage", choices=["graphsage", "gcn"])
@@ -112,7 +127,7 @@ def parse():
     ap.add_argument("--peer-rows", default=os.environ.get("GNN_PEER_ROWS", "direct"), choices=["alltoall", "direct"],
                     help="N > 1: peer feature rows read directly from the peers' buffers over xGMI (IPC-mapped "
                          "once; default, falls back to alltoall if any rank cannot map) or by an RCCL all-to-all "
-                         "per batch after a host negotiation; every N > 1 run also times the other form")
+                         "per batch after a host negotiation; every N > 1 run with --full also times the other form")
     ap.add_argument("--stage-ahead", type=int, default=int(os.environ.get("GNN_STAGE_AHEAD", "1")),
                     help="batches whose X0 staging / device side are issued ahead of the current step")
     ap.add_argument("--stage-gate", type=int,
@@ -135,9 +150,11 @@ def parse():
     ap.add_argument("--scale-factor", type=float, default=1.0,
                     help="sampler.py:119-121's boost of the skewed nodes' probability (the reference fixes 1.0); "
                          "> 1 takes the numpy restatement in Python producer threads")
-    ap.add_argument("--cprofile", default="", help="after the timed runs, cProfile 20 GPU steps into this file")
+    ap.add_argument("--cprofile", default="", help="--full: after the timed runs, cProfile 20 GPU steps into this file")
     ap.add_argument("--dump-batch", default="", help="save rank-0 batch 0 operands (.npz) for kernel profiling")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if not a.full:  # a plain run: the headline only
+        a.no_cpu_baseline = a.no_roofline = a.no_traffic = a.no_site_trace = a.no_gpu_step = True
     if a.samp_num is None:
         a.samp_num = 512 if a.cpu else 8192
     if a.batch_size is None:
@@ -181,7 +198,34 @@ def _dump_batch(hb, path):
              **{f"l{i}_shape": np.array(L.shape) for i, L in enumerate(hb.layers)})
 
 
-def pmc_traffic(hb, F, hidden, workdir="/tmp/gnn_bench_pmc"):
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay under this
+
+
+def step_outputs(loss, model):
+    """What a caller of the timed step holds after it: the loss it returned and the parameters it
+    left in the model, as host float32 arrays (copies: later passes train the same model on)."""
+    out = {"loss": np.asarray(loss.detach().cpu().numpy(), dtype=np.float32).reshape(-1)}
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    for i, (n, p) in enumerate(named):
+        out[f"param_{i:02d}_{n.replace('.', '_')}"] = p.detach().cpu().numpy().astype(np.float32, copy=True)
+    return out
+
+
+def dump_outputs(arrays, d, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: array} as d/<name>.npy (float32). Over `max_bytes` in all, every array that is
+    larger than its even share is cut to a sample of its flattened elements at fixed positions
+    (numpy default_rng(0), ascending), the same from run to run."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = (max_bytes - 4096 * len(arrays)) // max(len(arrays), 1) // 4  # elements; 4 KiB for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > max_bytes and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def pmc_traffic(hb, F, hidden, workdir=None):
     """Per-launch bytes leaving L2 (toward the Infinity Cache / HBM) and the L2 hit rate of
     each aggregation kernel instantiation, from rocprofv3 PMC counters in three passes
     (FETCH_SIZE; WRITE_SIZE; TCC_HIT_sum + TCC_MISS_sum) over scripts/pmc_probe.py: batch 0's
@@ -189,12 +233,17 @@ def pmc_traffic(hb, F, hidden, workdir="/tmp/gnn_bench_pmc"):
     by a calibration launch of the SAME kernel instantiation (4 rows x 256 B per wave
     instruction) over an operand whose every X row is gathered once from a 2.4 GB table, so
     its bytes are known (MI355X_MICROARCH.md §HBM: calibrate in your own access pattern).
-    Runs the probe as CHILD processes before this process has touched the GPU."""
+    Runs the probe as CHILD processes before this process has touched the GPU. `workdir`: where
+    the passes write (default: a temporary directory of this run, removed afterwards)."""
     import shutil
     import subprocess
+    import tempfile
 
     if shutil.which("rocprofv3") is None:
         return None
+    if workdir is None:
+        with tempfile.TemporaryDirectory(prefix="gnn_bench_pmc_") as d:
+            return pmc_traffic(hb, F, hidden, d)
     os.makedirs(workdir, exist_ok=True)
     npz = os.path.join(workdir, "batch0.npz")
     _dump_batch(hb, npz)
@@ -253,7 +302,7 @@ def pmc_traffic(hb, F, hidden, workdir="/tmp/gnn_bench_pmc"):
     return out
 
 
-def site_trace(workdir="/tmp/gnn_bench_sites", steps=30):
+def site_trace(workdir=None, steps=30):
     """Per call site, the aggregation kernels' durations as rocprofv3 --kernel-trace times them in
     the step: a CHILD run of this benchmark (same workload flags, the end-to-end pass only, `steps`
     timed steps) under the tracer, its dispatches cut into steps at adam_kernel and the aggregation
@@ -264,13 +313,25 @@ def site_trace(workdir="/tmp/gnn_bench_sites", steps=30):
     import glob
     import shutil
     import subprocess
+    import tempfile
 
     if shutil.which("rocprofv3") is None:
         return None
+    if workdir is None:  # a temporary directory of this run, removed afterwards
+        with tempfile.TemporaryDirectory(prefix="gnn_bench_sites_") as d:
+            return site_trace(d, steps)
     shutil.rmtree(workdir, ignore_errors=True)
+    # the child is a plain run (no --full: the end-to-end pass only) that writes no outputs
+    own, skip = [], False
+    for a in sys.argv[1:]:
+        if skip or a == "--full" or a.startswith("--dump-outputs="):
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        else:
+            own.append(a)
     cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", workdir, "-o", "t", "--",
-           sys.executable, os.path.abspath(__file__), *sys.argv[1:], "--steps", str(steps), "--warmup", "3",
-           "--no-cpu-baseline", "--no-traffic", "--no-gpu-step", "--no-site-trace"]
+           sys.executable, os.path.abspath(__file__), *own, "--steps", str(steps), "--warmup", "3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     if r.returncode != 0:
         log(f"site trace failed rc={r.returncode}: {r.stderr[-500:]}")
@@ -526,6 +587,8 @@ def run_cpu(args, spec, A, lap, labels, feats, num_classes, train):
         loss = step()
     el = time.perf_counter() - t0
     ld.close()
+    if args.dump_outputs:
+        dump_outputs(step_outputs(loss, model), args.dump_outputs)
     line = {"metric": METRIC, "value": round(args.steps / el, 3), "unit": "mini-batches/s", "n_gpus": 0,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -811,7 +874,7 @@ def _main(args, held):
     if world > 1:
         alltoall = staging.PeerExchange()
         requested, direct_err = args.peer_rows, None
-        if args.peer_rows == "direct" or os.environ.get("GNN_BENCH_PEER_AB", "1") == "1":
+        if args.peer_rows == "direct" or (args.full and os.environ.get("GNN_BENCH_PEER_AB", "1") == "1"):
             try:  # collective; every rank gets the same outcome
                 direct = staging.PeerDirect(store, feats=feats, buffer_nodes=pl.gpu_buffer_group)
             except RuntimeError as e:
@@ -1055,6 +1118,10 @@ def _main(args, held):
     torch.cuda.synchronize()
     live_ahead.clear()
     log(f"end to end: {world * args.steps / e2e_s:.1f} mini-batches/s ({time.time() - t0:.1f}s)")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss and the parameters it left, before any later pass trains on
+        dump_outputs(step_outputs(loss, model), args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # ------------------------------------------------- GPU step over distinct pre-sampled batches
     gpu_step, roof, spmm_detail, staging_info, dp_ab, peer_ab, prefetch_ab = None, None, {}, None, None, None, None
@@ -1297,7 +1364,7 @@ def _main(args, held):
     cpu = None
     sampler_cost = None
     dropin = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_cpu_baseline:
             cpu = cpu_baseline(args, probe_batch, feats, num_classes)
         if args.sampler == "ladies" and args.graph == "reddit" and not args.no_roofline:

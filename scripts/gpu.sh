@@ -7,12 +7,13 @@
 #   tests[:PYTEST_K]     pytest -m gpu (optionally -k PYTEST_K; ',' in it means ' or ')
 #   tfile:FILE[,FILE]    pytest -m gpu on the named test files only
 #   smoke                __graft_entry__.smoke()
-#   bench[:ARGS]         python bench.py ARGS (',' in ARGS means ' '), JSON line -> bench_TAG_N.json
+#   bench[:ARGS]         python bench.py ARGS (',' in ARGS means ' '; none: --full, the line with gpu_step,
+#                        the roofline and the CPU baseline), JSON line -> bench_TAG_N.json
 #   envbench:ENV:ARGS    bench with ENV (NAME=V+NAME=V) — for A/B/A/B runs of knobs
 #   kstats[:ARGS]        rocprofv3 --kernel-trace --stats of bench.py ARGS -> kstats_TAG_N.csv
 #   ktrace[:ARGS]        rocprofv3 --kernel-trace (per dispatch, trimmed CSV) -> ktrace_TAG_N.csv
 #   cpu1                 bench.py --cpu (BASELINE config 1 on the box's host)
-#   self2                GNN_DIST_BACKEND=gloo bench.py --gpus 2 (self-launched ranks on the one GPU)
+#   self2                GNN_DIST_BACKEND=gloo bench.py --gpus 2 --full (self-launched ranks on the one GPU)
 #   py:SCRIPT[:ARGS]     python SCRIPT ARGS (probes under scripts/)
 #   envpy:ENV:SCRIPT[:ARGS]  the same with ENV (NAME=V+NAME=V)
 set -o pipefail
@@ -42,6 +43,7 @@ for STEP in "$@"; do
     smoke)
       timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $out.log 2>&1; rc=$?; cat $out.log ;;
     bench)
+      [ -z "$arg" ] && arg=--full
       timeout -k 10 500 python -u bench.py $(sp "$arg") > $out.json 2> $out.err; rc=$?
       python3 -c "import json;d=json.loads(open('$out.json').read().strip().splitlines()[-1]);print('value',d['value'],'gpu_step',(d.get('gpu_step') or {}).get('value'))" 2>/dev/null ;;
     envbench)
@@ -70,7 +72,7 @@ EOF
     cpu1)
       timeout -k 10 300 python -u bench.py --cpu --steps 30 --warmup 3 > $out.json 2> $out.err; rc=$? ;;
     self2)
-      GNN_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --steps 20 --warmup 3 > $out.json 2> $out.err; rc=$? ;;
+      GNN_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --steps 20 --warmup 3 --full > $out.json 2> $out.err; rc=$? ;;
     py)
       script=${arg%%:*}; pargs=""; [ "$script" != "$arg" ] && pargs=${arg#*:}
       timeout -k 10 500 python -u $script $(sp "$pargs") > $out.log 2>&1; rc=$?; tail -5 $out.log ;;
