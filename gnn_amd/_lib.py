@@ -84,6 +84,8 @@ _SIGNATURES = {
                                     ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gnn_head_bce_bwd_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, ctypes.c_float,
                                     ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "gnn_head_eval_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _INT,
+                                 _VP]),
     # include/gnn_extract.h
     "gnn_ladies_extract_workspace_bytes": (_SZ, [_I64, _I64, _I64, ctypes.c_int32, _I64, _I64]),
     "gnn_colcount_create": (_INT, [ctypes.c_int32, _I64, _VP, _VP, ctypes.POINTER(_VP)]),
@@ -96,6 +98,8 @@ _SIGNATURES = {
     # include/gnn_step.h
     "gnn_train_step_workspace_bytes": (_SZ, [_VP]),
     "gnn_train_step_f32": (_INT, [_VP, _VP, _SZ, _VP]),
+    "gnn_eval_step_workspace_bytes": (_SZ, [_VP]),
+    "gnn_eval_step_f32": (_INT, [_VP, _VP, _I64, _VP, _INT, _VP, _SZ, _VP]),
     "gnn_gemm_f32_workspace_bytes": (_SZ, [_I64, _I64, _I64, _INT]),
     "gnn_gemm_f32": (_INT, [_INT, _INT, _I64, _I64, _I64, _INT, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _SZ, _VP]),
     "gnn_gemm_f32_split3_workspace_bytes": (_SZ, [_I64, _I64, _I64, _INT]),

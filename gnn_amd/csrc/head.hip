@@ -9,9 +9,15 @@
 // 168 KB for 41 classes x 1024, 704 KB for ogbn-papers' 172), and the per-row loss; a one-workgroup launch adds the rows in a fixed order. The
 // backward recomputes the normalised row, forms dz = w (sigmoid(z) - y), back-projects it
 // through W and the normalisation; dW = dzᵀ·xd and db = Σ dz are a small GEMM + sum.
+//
+// Evaluation (main.py:178-199, 217-241: model.eval(), forward, utils.loss, utils.calc_f1) runs the
+// same row pass without dropout and without the xd store, and leaves each row's predicted and
+// true class sets as 64-bit ballot masks; one workgroup per class then counts tp / fp / fn over
+// the rows (gnn_head_eval_f32): logits and labels never travel to the host for sklearn.
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cmath>
 #include <cstdint>
 
 #include "common.h"
@@ -74,18 +80,15 @@ __device__ __forceinline__ void load_w_block(f4 (&wv)[CB][PV], const float* __re
     }
 }
 
-template <int PV>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
-                                                       const float* __restrict__ W, const float* __restrict__ bias,
-                                                       int C, const float* __restrict__ Y, int64_t ldy_lab,
-                                                       float row_weight, float p, uint64_t seed, int training,
-                                                       float* __restrict__ XD, float* __restrict__ Z,
-                                                       float* __restrict__ nrm, float* __restrict__ rowloss) {
-  __shared__ float part[WPR][HEAD_MAXC + 1];  // [w][j] class partials, [w][HEAD_MAXC] sum of squares
+// The front half of both forward kernels: row r's norm, its normalised pieces (x), and the
+// four waves' partial dot products against every class in part[w][j] (synchronised on return).
+// DROP: the training forward's inverted dropout and its store of the dropped-out row to XD.
+template <int PV, bool DROP>
+__device__ __forceinline__ float head_row_partials(const float* __restrict__ X, int64_t ldx, int r, int D,
+                                                   const float* __restrict__ W, int C, float p, uint64_t seed,
+                                                   bool tr, float* __restrict__ XD,
+                                                   float (&part)[WPR][HEAD_MAXC + 1]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = blockIdx.x;
-  const float inv_keep = 1.0f / (1.0f - p);
-  const bool tr = training != 0 && p > 0.0f;
   f4 x[PV];
   float ss = 0.0f;
 #pragma unroll
@@ -107,12 +110,15 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     const int c = ((w + i * WPR) * 64 + lane) * 4;
     if (c < D) {
       f4 v = x[i] * inv;
-      v.x *= drop_mult(seed, r, D, c + 0, p, tr, inv_keep);
-      v.y *= drop_mult(seed, r, D, c + 1, p, tr, inv_keep);
-      v.z *= drop_mult(seed, r, D, c + 2, p, tr, inv_keep);
-      v.w *= drop_mult(seed, r, D, c + 3, p, tr, inv_keep);
+      if constexpr (DROP) {
+        const float inv_keep = 1.0f / (1.0f - p);
+        v.x *= drop_mult(seed, r, D, c + 0, p, tr, inv_keep);
+        v.y *= drop_mult(seed, r, D, c + 1, p, tr, inv_keep);
+        v.z *= drop_mult(seed, r, D, c + 2, p, tr, inv_keep);
+        v.w *= drop_mult(seed, r, D, c + 3, p, tr, inv_keep);
+        *reinterpret_cast<f4*>(XD + (int64_t)r * D + c) = v;
+      }
       x[i] = v;
-      *reinterpret_cast<f4*>(XD + (int64_t)r * D + c) = v;
     }
   }
   // software-pipelined over blocks of 8 classes: the next block's W loads are in flight while
@@ -149,6 +155,31 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     if ((lane & 7) == 0 && j0 + (lane >> 3) < C) part[w][j0 + (lane >> 3)] = t1;
   }
   __syncthreads();
+  return norm;
+}
+
+// logit j of the row from the four waves' partials, and its BCE-with-logits term (stable form:
+// max(z, 0) - z y + log1p(exp(-|z|)))
+__device__ __forceinline__ float head_logit(const float (&part)[WPR][HEAD_MAXC + 1], int j,
+                                            const float* __restrict__ bias) {
+  return ((part[0][j] + part[1][j]) + (part[2][j] + part[3][j])) + (bias ? bias[j] : 0.0f);
+}
+__device__ __forceinline__ float bce_term(float z, float y) {
+  return fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
+}
+
+template <int PV>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
+                                                       const float* __restrict__ W, const float* __restrict__ bias,
+                                                       int C, const float* __restrict__ Y, int64_t ldy_lab,
+                                                       float row_weight, float p, uint64_t seed, int training,
+                                                       float* __restrict__ XD, float* __restrict__ Z,
+                                                       float* __restrict__ nrm, float* __restrict__ rowloss) {
+  __shared__ float part[WPR][HEAD_MAXC + 1];  // [w][j] class partials, [w][HEAD_MAXC] sum of squares
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = blockIdx.x;
+  const bool tr = training != 0 && p > 0.0f;
+  const float norm = head_row_partials<PV, true>(X, ldx, r, D, W, C, p, seed, tr, XD, part);
   if (w != 0) return;
   // lane j: logits j, j + 64, ... and their BCE terms
   float term = 0.0f;
@@ -156,11 +187,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   for (int q = 0; q < HEAD_CQ; ++q) {
     const int j = lane + 64 * q;
     if (j < C) {
-      const float z = ((part[0][j] + part[1][j]) + (part[2][j] + part[3][j])) + (bias ? bias[j] : 0.0f);
+      const float z = head_logit(part, j, bias);
       Z[(int64_t)r * C + j] = z;
-      const float y = Y[(int64_t)r * ldy_lab + j];
-      // BCE with logits, stable form: max(z, 0) - z y + log1p(exp(-|z|))
-      term += fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
+      term += bce_term(z, Y[(int64_t)r * ldy_lab + j]);
     }
   }
   const float loss = wave_sum(term);
@@ -170,8 +199,86 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void head_loss_sum_kernel(const float* __restrict__ rowloss, int M,
-                                                            float* __restrict__ out) {
+// (value, index) of the wave's largest value; the lowest index wins ties (np.argmax)
+__device__ __forceinline__ int wave_argmax(float v, int i) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ov = __shfl_xor(v, m);
+    const int oi = __shfl_xor(i, m);
+    if (ov > v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+  return i;
+}
+
+// The evaluation forward (gnn_head_eval_f32): head_fwd_kernel's row pass without dropout and
+// without the xd / norm stores; logits to Z (row stride ldz) when Z is given; with labels, the
+// row's loss terms and its predicted / true class sets as bit masks: rowmask[r][q] (q < 4) bit b
+// = class 64 q + b predicted, rowmask[r][4 + q] = class 64 q + b true. mode 0: z > 0 / y > 0.5
+// per class; mode 1: the one-hot argmax of the logits / of the labels.
+template <int PV>
+__global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
+                                                        const float* __restrict__ W, const float* __restrict__ bias,
+                                                        int C, const float* __restrict__ Y, int64_t ldy_lab,
+                                                        float row_weight, int mode, float* __restrict__ Z,
+                                                        int64_t ldz, float* __restrict__ rowloss,
+                                                        unsigned long long* __restrict__ rowmask) {
+  __shared__ float part[WPR][HEAD_MAXC + 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = blockIdx.x;
+  head_row_partials<PV, false>(X, ldx, r, D, W, C, 0.0f, 0, false, nullptr, part);
+  if (w != 0) return;
+  float term = 0.0f, bz = -INFINITY, by = -INFINITY;
+  int zi = INT_MAX, yi = INT_MAX;
+  bool pj[HEAD_CQ], tj[HEAD_CQ];
+#pragma unroll
+  for (int q = 0; q < HEAD_CQ; ++q) {
+    const int j = lane + 64 * q;
+    pj[q] = tj[q] = false;
+    if (j < C) {
+      const float z = head_logit(part, j, bias);
+      if (Z) Z[(int64_t)r * ldz + j] = z;
+      if (Y) {
+        const float y = Y[(int64_t)r * ldy_lab + j];
+        term += bce_term(z, y);
+        pj[q] = z > 0.0f;
+        tj[q] = y > 0.5f;
+        if (z > bz) bz = z, zi = j;  // ascending j per lane: the first of equal values stays
+        if (y > by) by = y, yi = j;
+      }
+    }
+  }
+  if (!Y) return;
+  if (mode == 1) {
+    zi = wave_argmax(bz, zi);
+    yi = wave_argmax(by, yi);
+#pragma unroll
+    for (int q = 0; q < HEAD_CQ; ++q) {
+      pj[q] = lane + 64 * q == zi;
+      tj[q] = lane + 64 * q == yi;
+    }
+  }
+  unsigned long long pm[HEAD_CQ], tm[HEAD_CQ];
+#pragma unroll
+  for (int q = 0; q < HEAD_CQ; ++q) {
+    pm[q] = __ballot(pj[q]);
+    tm[q] = __ballot(tj[q]);
+  }
+  const float loss = wave_sum(term);
+  if (lane == 0) {
+    rowloss[r] = loss * row_weight;
+#pragma unroll
+    for (int q = 0; q < HEAD_CQ; ++q) {
+      rowmask[(int64_t)r * (2 * HEAD_CQ) + q] = pm[q];
+      rowmask[(int64_t)r * (2 * HEAD_CQ) + HEAD_CQ + q] = tm[q];
+    }
+  }
+}
+
+// the fixed-order sum of the per-row loss terms (one workgroup of 256)
+__device__ __forceinline__ void block_loss_sum(const float* __restrict__ rowloss, int M, float* __restrict__ out) {
   __shared__ float red[4];
   float s = 0.0f;
   for (int i = threadIdx.x; i < M; i += 256) s += rowloss[i];
@@ -179,6 +286,46 @@ __global__ __launch_bounds__(256) void head_loss_sum_kernel(const float* __restr
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void head_loss_sum_kernel(const float* __restrict__ rowloss, int M,
+                                                            float* __restrict__ out) {
+  block_loss_sum(rowloss, M, out);
+}
+
+// Second stage of the evaluation head: workgroup c < C counts class c over the rows' masks —
+// tp = predicted and true, fp = predicted only, fn = true only — each thread a strided set of
+// rows, then an integer tree: exact whatever the order, and written, not accumulated.
+// Workgroup C is head_loss_sum_kernel.
+__global__ __launch_bounds__(256) void head_eval_reduce_kernel(const float* __restrict__ rowloss,
+                                                               const unsigned long long* __restrict__ rowmask,
+                                                               int M, int C, float* __restrict__ loss,
+                                                               int* __restrict__ counts) {
+  if ((int)blockIdx.x == C) {
+    block_loss_sum(rowloss, M, loss);
+    return;
+  }
+  __shared__ int red[3][4];
+  const int c = blockIdx.x, word = c >> 6, bit = c & 63;
+  int n[3] = {0, 0, 0};
+  for (int r = threadIdx.x; r < M; r += 256) {
+    const bool pj = (rowmask[(int64_t)r * (2 * HEAD_CQ) + word] >> bit) & 1;
+    const bool tj = (rowmask[(int64_t)r * (2 * HEAD_CQ) + HEAD_CQ + word] >> bit) & 1;
+    n[0] += pj && tj;
+    n[1] += pj && !tj;
+    n[2] += tj && !pj;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) n[k] += __shfl_xor(n[k], m);
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = n[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int k = threadIdx.x;
+    counts[(int64_t)k * C + c] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+  }
 }
 
 template <int PV>
@@ -287,6 +434,38 @@ int gnn_head_bce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, cons
   }
   head_loss_sum_kernel<<<dim3(1), dim3(256), 0, st>>>(rowloss, (int)M, loss);
   GNN_LAUNCHED("head_loss_sum_kernel");
+  return 0;
+}
+
+int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                      int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
+                      uint64_t* rowmask, float* loss, int32_t* counts, int mode, void* stream) {
+  GNN_REQUIRE(M >= 0 && D > 0 && C > 0, "gnn_head_eval_f32: bad sizes");
+  GNN_REQUIRE(D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV, "gnn_head_eval_f32: D must be a multiple of 4, <= %d",
+              64 * 4 * HEAD_MAXV);
+  GNN_REQUIRE(C <= HEAD_MAXC, "gnn_head_eval_f32: at most %d classes", HEAD_MAXC);
+  GNN_REQUIRE(ldx % 4 == 0 && ldx >= D && (uintptr_t)X % 16 == 0 && (uintptr_t)W % 16 == 0,
+              "gnn_head_eval_f32: X, W must be 16-byte aligned with ldx % 4 == 0, ldx >= D");
+  GNN_REQUIRE(M < INT_MAX && (mode == 0 || mode == 1), "gnn_head_eval_f32: bad M or mode %d", mode);
+  GNN_REQUIRE(!z || ldz >= C, "gnn_head_eval_f32: ldz < C");
+  // the loss and the counts come with labels (an empty batch still zeroes them)
+  const bool scored = labels != nullptr || (M == 0 && loss != nullptr);
+  if (scored)
+    GNN_REQUIRE(loss && counts && (M == 0 || (rowloss && rowmask && ldl >= C)) && (uintptr_t)rowmask % 8 == 0,
+                "gnn_head_eval_f32: labels need loss, counts, rowloss, rowmask and ldl >= C");
+  hipStream_t st = (hipStream_t)stream;
+  if (M > 0 && (scored || z)) {
+    auto k = D <= 64 * 4 * WPR ? head_eval_kernel<1> : head_eval_kernel<2>;
+    k<<<dim3((unsigned)M), dim3(64 * WPR), 0, st>>>(X, ldx, (int)M, (int)D, W, bias, (int)C, labels, ldl,
+                                                    1.0f / (float)M, mode, z, ldz, rowloss,
+                                                    (unsigned long long*)rowmask);
+    GNN_LAUNCHED("head_eval_kernel");
+  }
+  if (scored) {
+    head_eval_reduce_kernel<<<dim3((unsigned)C + 1), dim3(256), 0, st>>>(
+        rowloss, (const unsigned long long*)rowmask, (int)M, (int)C, loss, counts);
+    GNN_LAUNCHED("head_eval_reduce_kernel");
+  }
   return 0;
 }
 

@@ -25,6 +25,11 @@
 //                         dW_B, dW_W = [dhB, dhW]ᵀ·[xs, feat]  (split-k split3 from 2048 rows)
 //                         l >= 1: dxs, dfeat = [dhB, dhW]·[W_B, W_W];
 //                                 dY_{l-1} = A_lᵀ·dfeat (+ dxs scattered through rmap, SAGE)
+//
+// gnn_eval_step_f32 (validation / test batches, main.py:178-199, 217-241) is the forward above
+// with training = 0 — forward() below, called by both entry points — followed by the evaluation
+// head (gnn_head_eval_f32: loss, logits, per-class prediction counts), on a plan without
+// backward buffers.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 
@@ -247,10 +252,19 @@ struct Plan {
   int nl = 0, sage = 1;
   LayerBufs lb[GNN_STEP_MAX_LAYERS];
   float *xd, *z, *nrm, *rowloss, *dz, *dXh;
+  uint64_t* rowmask;  // the evaluation head's per-row class masks (gnn_head_eval_f32)
   int64_t Mh = 0, Dh = 0, C = 0;
 };
 
-int plan(const int64_t* d, Arena& ar, Plan& pl) {
+#define GNN_TRY(x)        \
+  do {                    \
+    int rc_ = (x);        \
+    if (rc_) return rc_;  \
+  } while (0)
+
+// The descriptor's shapes: what the layers' and the head's kernels are called with, no buffer
+// yet (the training and the evaluation plan carve differently). measuring: X0 is taken as aligned.
+int shapes(const int64_t* d, bool measuring, Plan& pl) {
   GNN_REQUIRE(d[GNN_SH_VERSION] == GNN_STEP_VERSION, "gnn_train_step: descriptor version %lld",
               (long long)d[GNN_SH_VERSION]);
   pl.nl = (int)d[GNN_SH_LAYERS];
@@ -274,7 +288,7 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
       const LayerBufs& p = pl.lb[l - 1];
       GNN_REQUIRE(b.K == p.M, "gnn_train_step: layer %d has K = %lld, layer %d M = %lld", l, (long long)b.K, l - 1,
                   (long long)p.M);
-      b.X = p.Y;
+      b.X = nullptr;  // the layer below's output: a 256-byte aligned workspace buffer, set by the plan
       b.ldx = p.D;
       b.F = p.D;
     }
@@ -282,21 +296,12 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
     // the aggregation's padded width (custom_sparse_ops.spmm_csr): 16-byte loads over whole
     // line-aligned rows when the input rows are padded (the 602-wide features in 608-float rows)
     b.Fk = b.F;
-    if (b.F % 4 && b.ldx % 4 == 0 && ((uintptr_t)b.X % 16 == 0 || !ar.base) && b.ldx >= b.F + (4 - b.F % 4))
+    if (b.F % 4 && b.ldx % 4 == 0 && (l >= 1 || (uintptr_t)b.X % 16 == 0 || measuring) &&
+        b.ldx >= b.F + (4 - b.F % 4))
       b.Fk = b.F + (4 - b.F % 4);
     b.ldo = (b.Fk != b.F && b.ldx <= 2 * b.Fk) ? b.ldx : b.Fk;
-    b.feat = ar.take<float>(b.M * b.ldo);
-    b.xs = pl.sage ? ar.take<float>(b.M * b.ldo) : nullptr;
-    b.hB = pl.sage ? ar.take<float>(b.M * N) : nullptr;
-    b.hW = ar.take<float>(b.M * N);
-    b.Y = ar.take<float>(b.M * b.D);
-    b.mean = ar.take<float>(b.M);
-    b.rstd = ar.take<float>(b.M);
     b.b_fwd = gnn_spmm_workspace_bytes(b.M, b.nnz, b.Fk, 0);
-    b.ws_fwd = ar.take<char>((int64_t)b.b_fwd);
     b.b_gemm_f = gemm_ws(b.M, N, b.F, n);
-    b.ws_gemm_f = ar.take<char>((int64_t)b.b_gemm_f);
-    b.ws_gemm_f2 = pl.sage ? ar.take<char>((int64_t)b.b_gemm_f) : nullptr;  // the aux stream's product
   }
   const LayerBufs& top = pl.lb[pl.nl - 1];
   pl.Mh = top.M;
@@ -304,6 +309,66 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
   pl.C = d[GNN_SH_CLASSES];
   GNN_REQUIRE(pl.C > 0 && pl.C <= 256 && pl.Dh % 4 == 0 && pl.Dh <= 2048, "gnn_train_step: head %lld x %lld",
               (long long)pl.Dh, (long long)pl.C);
+  return 0;
+}
+
+// The evaluation step's plan (gnn_eval_step_f32): no backward buffer, and ONE set of forward
+// buffers for all layers (sized for the largest), the layer outputs in two that alternate. Safe
+// with the forward's aux stream: each layer joins it before its tail, and the next layer forks
+// it again from the step's stream, so no buffer is rewritten while the other stream may read it.
+int plan_eval(const int64_t* d, Arena& ar, Plan& pl) {
+  GNN_TRY(shapes(d, !ar.base, pl));
+  int64_t feat = 0, h = 0, rows = 0, y[2] = {0, 0};
+  size_t wf = 0, wg = 0;
+  for (int l = 0; l < pl.nl; ++l) {
+    const LayerBufs& b = pl.lb[l];
+    feat = std::max(feat, b.M * b.ldo);
+    h = std::max(h, b.M * b.N);
+    rows = std::max(rows, b.M);
+    y[l & 1] = std::max(y[l & 1], b.M * b.D);
+    wf = std::max(wf, b.b_fwd);
+    wg = std::max(wg, b.b_gemm_f);
+  }
+  LayerBufs s = {};
+  s.feat = ar.take<float>(feat);
+  s.xs = pl.sage ? ar.take<float>(feat) : nullptr;
+  s.hB = pl.sage ? ar.take<float>(h) : nullptr;
+  s.hW = ar.take<float>(h);
+  float* const Y[2] = {ar.take<float>(y[0]), ar.take<float>(y[1])};
+  s.mean = ar.take<float>(rows);
+  s.rstd = ar.take<float>(rows);
+  s.ws_fwd = ar.take<char>((int64_t)wf);
+  s.ws_gemm_f = ar.take<char>((int64_t)wg);
+  s.ws_gemm_f2 = pl.sage ? ar.take<char>((int64_t)wg) : nullptr;
+  for (int l = 0; l < pl.nl; ++l) {
+    LayerBufs& b = pl.lb[l];
+    if (l) b.X = pl.lb[l - 1].Y;
+    b.feat = s.feat, b.xs = s.xs, b.hB = s.hB, b.hW = s.hW, b.Y = Y[l & 1], b.mean = s.mean, b.rstd = s.rstd;
+    b.ws_fwd = s.ws_fwd, b.ws_gemm_f = s.ws_gemm_f, b.ws_gemm_f2 = s.ws_gemm_f2;
+  }
+  pl.rowloss = ar.take<float>(pl.Mh);
+  pl.rowmask = ar.take<uint64_t>(pl.Mh * 8);
+  return 0;
+}
+
+int plan(const int64_t* d, Arena& ar, Plan& pl) {
+  GNN_TRY(shapes(d, !ar.base, pl));
+  const int64_t N = d[GNN_SH_NHID];
+  const int n = pl.sage ? 2 : 1;
+  for (int l = 0; l < pl.nl; ++l) {
+    LayerBufs& b = pl.lb[l];
+    if (l) b.X = pl.lb[l - 1].Y;
+    b.feat = ar.take<float>(b.M * b.ldo);
+    b.xs = pl.sage ? ar.take<float>(b.M * b.ldo) : nullptr;
+    b.hB = pl.sage ? ar.take<float>(b.M * N) : nullptr;
+    b.hW = ar.take<float>(b.M * N);
+    b.Y = ar.take<float>(b.M * b.D);
+    b.mean = ar.take<float>(b.M);
+    b.rstd = ar.take<float>(b.M);
+    b.ws_fwd = ar.take<char>((int64_t)b.b_fwd);
+    b.ws_gemm_f = ar.take<char>((int64_t)b.b_gemm_f);
+    b.ws_gemm_f2 = pl.sage ? ar.take<char>((int64_t)b.b_gemm_f) : nullptr;  // the aux stream's product
+  }
   pl.xd = ar.take<float>(pl.Mh * pl.Dh);
   pl.z = ar.take<float>(pl.Mh * pl.C);
   pl.nrm = ar.take<float>(pl.Mh);
@@ -337,96 +402,69 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
   return 0;
 }
 
-#define GNN_TRY(x)        \
-  do {                    \
-    int rc_ = (x);        \
-    if (rc_) return rc_;  \
-  } while (0)
-
-}  // namespace
-
-extern "C" {
-
-size_t gnn_train_step_workspace_bytes(const int64_t* desc) {
-  if (!desc) return 0;
-  Arena ar{nullptr};
+// What one call holds while it issues its kernels: the plan, the streams, the vendor-GEMM handles
+// (held with the aux stream's lock), and the descriptor's optional hooks.
+struct Run {
+  const int64_t* d = nullptr;
   Plan pl;
-  if (plan(desc, ar, pl)) return 0;
-  return ar.off;
-}
-
-int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes, void* stream) {
-  GNN_REQUIRE(d != nullptr, "gnn_train_step: NULL descriptor");
-  Arena ar{(char*)workspace};
-  Plan pl;
-  {
-    Arena dry{nullptr};
-    Plan tmp;
-    GNN_TRY(plan(d, dry, tmp));
-    GNN_REQUIRE(workspace && workspace_bytes >= dry.off, "gnn_train_step: workspace too small (%zu < %zu)",
-                workspace_bytes, dry.off);
-    GNN_REQUIRE((uintptr_t)workspace % 256 == 0, "gnn_train_step: workspace not 256-byte aligned");
-  }
-  GNN_TRY(plan(d, ar, pl));
-  hipStream_t st = (hipStream_t)stream;
-  rocblas_handle h = nullptr;
-  GNN_TRY(blas_handle(&h));
-  if (rocblas_set_stream(h, st) != rocblas_status_success) return gnn::fail(-1, "rocblas_set_stream failed");
-  const int n = pl.sage ? 2 : 1;
-  const float p = [&] {
-    float f;
-    const int32_t bits = (int32_t)d[GNN_SH_PDROP_BITS];
-    std::memcpy(&f, &bits, 4);
-    return f;
-  }();
-  const int training = (int)d[GNN_SH_TRAINING];
+  hipStream_t st = nullptr;
+  rocblas_handle h = nullptr, ha = nullptr;  // ha: the aux stream's handle (small products there)
   Aux* aux = nullptr;
-  const bool big_ov = overlap_enabled() && !f32_gemm();  // the big layers' GEMMs beside their SpMMs (off)
-  const bool small_ov = small_overlap_enabled();
-  if (big_ov || small_ov) GNN_TRY(aux_of(st, &aux));
   std::unique_lock<std::mutex> aux_lock;
-  if (aux) aux_lock = std::unique_lock<std::mutex>(aux->mu);
-  bool aux_used = false;
-  rocblas_handle ha = nullptr;  // the aux stream's handle (small products there)
-  if (aux && small_ov) {
-    GNN_TRY(blas_handle(&ha, 1));
-    if (rocblas_set_stream(ha, aux->s) != rocblas_status_success) return gnn::fail(-1, "rocblas_set_stream failed");
+  bool big_ov = false;  // the big layers' GEMMs beside their SpMMs (off)
+  float p = 0.0f;
+  int training = 0;
+  int64_t phase = 0;
+  int64_t* T = nullptr;  // per-aggregation timing records (GNN_SH_TIMING)
+  int64_t nrec = 0;
+
+  int open(const int64_t* desc, hipStream_t stream) {
+    d = desc;
+    st = stream;
+    GNN_TRY(blas_handle(&h));
+    if (rocblas_set_stream(h, st) != rocblas_status_success) return gnn::fail(-1, "rocblas_set_stream failed");
+    const int32_t bits = (int32_t)d[GNN_SH_PDROP_BITS];
+    std::memcpy(&p, &bits, 4);
+    big_ov = overlap_enabled() && !f32_gemm();
+    const bool small_ov = small_overlap_enabled();
+    if (big_ov || small_ov) GNN_TRY(aux_of(st, &aux));
+    if (aux) aux_lock = std::unique_lock<std::mutex>(aux->mu);
+    if (aux && small_ov) {
+      GNN_TRY(blas_handle(&ha, 1));
+      if (rocblas_set_stream(ha, aux->s) != rocblas_status_success) return gnn::fail(-1, "rocblas_set_stream failed");
+    }
+    return 0;
   }
   // optional per-aggregation timing (GNN_SH_TIMING): arm the caller's event pair for the next
   // SpMM launch (gnn_spmm_set_timing_events) and record the call's shape beside it
-  int64_t* const T = HP<int64_t>(d, GNN_SH_TIMING);
-  int64_t nrec = 0;
-  auto arm = [&](int64_t kind, int64_t l, int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t Fk, int64_t ldx,
-                 int64_t ldo, const void* X, const void* Y, int64_t res_rows) {
+  void arm(int64_t kind, int64_t l, int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t Fk, int64_t ldx,
+           int64_t ldo, const void* X, const void* Y, int64_t res_rows) {
     if (!T || nrec >= T[0]) return;
     int64_t* r = T + 1 + GNN_STEP_TIMING_SLOTS * nrec++;
     gnn_spmm_set_timing_events((void*)r[0], (void*)r[1]);
     const int64_t v[] = {kind, l, M, K, nnz, F, Fk, ldx, ldo, (int64_t)(uintptr_t)X, (int64_t)(uintptr_t)Y, res_rows, 1};
     std::memcpy(r + 2, v, sizeof v);
-  };
+  }
   // the staging gate (GNN_SH_STAGE_EVENT): recorded right after the chosen layer's forward
   // aggregation is issued
-  auto stage_gate = [&](int l) -> int {
+  int stage_gate(int l) {
     if (d[GNN_SH_STAGE_EVENT] && l == (int)d[GNN_SH_STAGE_LAYER])
       GNN_HIP(hipEventRecord((hipEvent_t)d[GNN_SH_STAGE_EVENT], st), "hipEventRecord (stage gate)");
     return 0;
-  };
-  // phase (GNN_SH_PHASE): 1 = only layer 0's forward aggregation, into this workspace (a data-
-  // parallel caller issues the next batch's while the gradient all-reduce runs); 2 = the step with
-  // that aggregation already issued into this workspace by a phase-1 call (same descriptor plan)
-  const int64_t phase = d[GNN_SH_PHASE];
-  GNN_REQUIRE(phase >= 0 && phase <= 2, "gnn_train_step: phase %lld", (long long)phase);
-  auto first_agg = [&]() -> int {
-    const LayerBufs& b = pl.lb[0];
-    return gnn_spmm_csr_f32(P<const int32_t>(d, 0, GNN_SL_ROWPTR), P<const int32_t>(d, 0, GNN_SL_COL),
-                            P<const float>(d, 0, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
-                            b.ws_fwd, b.b_fwd, 0, st);
-  };
-  if (phase == 1) {
-    GNN_TRY(first_agg());
-    return stage_gate(0);
   }
-  // ------------------------------------------------------------------ forward
+};
+
+// The layers' forward, bottom-up, into the plan's buffers: shared by the training step and the
+// evaluation step (training = 0), so both issue the same kernels with the same routing.
+int forward(Run& r) {
+  const int64_t* const d = r.d;
+  Plan& pl = r.pl;
+  hipStream_t st = r.st;
+  rocblas_handle h = r.h, ha = r.ha;
+  Aux* aux = r.aux;
+  const bool big_ov = r.big_ov;
+  const int64_t phase = r.phase;
+  const int n = pl.sage ? 2 : 1;
   for (int l = 0; l < pl.nl; ++l) {
     LayerBufs& b = pl.lb[l];
     const int64_t N = b.N;
@@ -451,11 +489,11 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
       GNN_TRY(gnn::gemm_split3_as_batch(0, 0, b.M, N, b.F, 1, 2, 0, Ab, b.ldo, Bb, b.F, Cb, N, b.ws_gemm_f2, b.b_gemm_f,
                                         aux->s));
       if (phase != 2 || l != 0) {
-        arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
+        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
         GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
                                  P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
                                  b.ws_fwd, b.b_fwd, 0, st));
-        GNN_TRY(stage_gate(l));
+        GNN_TRY(r.stage_gate(l));
       }
       const float* Aw[1] = {b.feat};
       const float* Bw[1] = {WW};
@@ -469,21 +507,21 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
                                   b.F, aux->s));
       GNN_TRY(mm_xwt(ha, b.xs, b.ldo, WB, b.F, b.hB, N, b.M, N, b.F));
       if (phase != 2 || l != 0) {
-        arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
+        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
         GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
                                  P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
                                  b.ws_fwd, b.b_fwd, 0, st));
-        GNN_TRY(stage_gate(l));
+        GNN_TRY(r.stage_gate(l));
       }
       GNN_TRY(mm_xwt(h, b.feat, b.ldo, WW, b.F, b.hW, N, b.M, N, b.F));
       GNN_TRY(fork_join(aux, aux->s, st));  // the tail reads hB
     } else {
       if (phase != 2 || l != 0) {
-        arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
+        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
         GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
                                  P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
                                  b.ws_fwd, b.b_fwd, 0, st));
-        GNN_TRY(stage_gate(l));
+        GNN_TRY(r.stage_gate(l));
       }
       // x[sampled] feeds only linearB and its weight gradient: when both run on split3 (and X's
       // rows have the aggregation output's stride) the GEMMs read X's rows through the index
@@ -514,9 +552,68 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
     }
     GNN_TRY(gnn_sage_norm_fwd_f32(pl.sage ? b.hB : nullptr, pl.sage ? N : 4, pl.sage ? N : 0, b.hW, N, N,
                                   pl.sage ? P<const float>(d, l, GNN_SL_BB) : nullptr, P<const float>(d, l, GNN_SL_BW),
-                                  P<const float>(d, l, GNN_SL_SCALE), P<const float>(d, l, GNN_SL_OFFSET), b.M, p,
-                                  (uint64_t)L(d, l, GNN_SL_SEED), training, b.Y, b.D, b.mean, b.rstd, st));
+                                  P<const float>(d, l, GNN_SL_SCALE), P<const float>(d, l, GNN_SL_OFFSET), b.M, r.p,
+                                  (uint64_t)L(d, l, GNN_SL_SEED), r.training, b.Y, b.D, b.mean, b.rstd, st));
   }
+  return 0;
+}
+
+// The workspace is validated before anything is launched: large enough for the plan, aligned.
+int check_workspace(const void* workspace, size_t workspace_bytes, size_t need) {
+  GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_train_step: workspace too small (%zu < %zu)",
+              workspace_bytes, need);
+  GNN_REQUIRE((uintptr_t)workspace % 256 == 0, "gnn_train_step: workspace not 256-byte aligned");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gnn_train_step_workspace_bytes(const int64_t* desc) {
+  if (!desc) return 0;
+  Arena ar{nullptr};
+  Plan pl;
+  if (plan(desc, ar, pl)) return 0;
+  return ar.off;
+}
+
+int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes, void* stream) {
+  GNN_REQUIRE(d != nullptr, "gnn_train_step: NULL descriptor");
+  Arena ar{(char*)workspace};
+  Run r;
+  Plan& pl = r.pl;
+  {
+    Arena dry{nullptr};
+    Plan tmp;
+    GNN_TRY(plan(d, dry, tmp));
+    GNN_TRY(check_workspace(workspace, workspace_bytes, dry.off));
+  }
+  GNN_TRY(plan(d, ar, pl));
+  hipStream_t st = (hipStream_t)stream;
+  GNN_TRY(r.open(d, st));
+  rocblas_handle h = r.h, ha = r.ha;
+  Aux* aux = r.aux;
+  const bool big_ov = r.big_ov;
+  const int n = pl.sage ? 2 : 1;
+  const float p = r.p;
+  const int training = r.training = (int)d[GNN_SH_TRAINING];
+  bool aux_used = false;
+  r.T = HP<int64_t>(d, GNN_SH_TIMING);
+  // phase (GNN_SH_PHASE): 1 = only layer 0's forward aggregation, into this workspace (a data-
+  // parallel caller issues the next batch's while the gradient all-reduce runs); 2 = the step with
+  // that aggregation already issued into this workspace by a phase-1 call (same descriptor plan)
+  const int64_t phase = r.phase = d[GNN_SH_PHASE];
+  GNN_REQUIRE(phase >= 0 && phase <= 2, "gnn_train_step: phase %lld", (long long)phase);
+  if (phase == 1) {
+    const LayerBufs& b = pl.lb[0];
+    GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, 0, GNN_SL_ROWPTR), P<const int32_t>(d, 0, GNN_SL_COL),
+                             P<const float>(d, 0, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
+                             b.ws_fwd, b.b_fwd, 0, st));
+    return r.stage_gate(0);
+  }
+  // ------------------------------------------------------------------ forward
+  GNN_TRY(forward(r));
   // ------------------------------------------------------------------ head + loss
   const LayerBufs& top = pl.lb[pl.nl - 1];
   const float* Wh = HP<const float>(d, GNN_SH_HEAD_W);
@@ -642,12 +739,12 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
         prev.agg_rmap = pl.sage ? P<const int32_t>(d, l, GNN_SL_RMAP) : nullptr;
       } else if (pl.sage) {
         GNN_REQUIRE(P<const int32_t>(d, l, GNN_SL_RMAP) != nullptr, "gnn_train_step: layer %d has no row map", l);
-        arm(1, l, b.K, b.M, b.nnz, b.F, b.F, b.F, b.F, b.dfeat, prev.dY, b.M);
+        r.arm(1, l, b.K, b.M, b.nnz, b.F, b.F, b.F, b.F, b.dfeat, prev.dY, b.M);
         GNN_TRY(gnn_spmm_csr_f32_ex(P<const int32_t>(d, l, GNN_SL_TROWPTR), P<const int32_t>(d, l, GNN_SL_TCOL),
                                     P<const float>(d, l, GNN_SL_TVAL), b.K, b.M, b.nnz, b.dfeat, b.F, prev.dY, b.F,
                                     b.F, b.dxs, b.F, P<const int32_t>(d, l, GNN_SL_RMAP), b.ws_bwd, b.b_bwd, 0, st));
       } else {
-        arm(1, l, b.K, b.M, b.nnz, b.F, b.F, b.F, b.F, b.dfeat, prev.dY, 0);
+        r.arm(1, l, b.K, b.M, b.nnz, b.F, b.F, b.F, b.F, b.dfeat, prev.dY, 0);
         GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_TROWPTR), P<const int32_t>(d, l, GNN_SL_TCOL),
                                  P<const float>(d, l, GNN_SL_TVAL), b.K, b.M, b.nnz, b.dfeat, b.F, prev.dY, b.F, b.F,
                                  b.ws_bwd, b.b_bwd, 0, st));
@@ -661,6 +758,44 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
   }
   if (aux_used) GNN_TRY(fork_join(aux, aux->s, st));
   return 0;
+}
+
+size_t gnn_eval_step_workspace_bytes(const int64_t* desc) {
+  if (!desc) return 0;
+  Arena ar{nullptr};
+  Plan pl;
+  if (plan_eval(desc, ar, pl)) return 0;
+  return ar.off;
+}
+
+int gnn_eval_step_f32(const int64_t* d, float* logits, int64_t ldz, int32_t* counts, int mode, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  GNN_REQUIRE(d != nullptr, "gnn_eval_step: NULL descriptor");
+  GNN_REQUIRE(d[GNN_SH_PHASE] == 0, "gnn_eval_step: phase %lld (must be 0)", (long long)d[GNN_SH_PHASE]);
+  GNN_REQUIRE(mode == 0 || mode == 1, "gnn_eval_step: mode %d", mode);
+  const float* labels = HP<const float>(d, GNN_SH_LABELS);
+  float* loss = HP<float>(d, GNN_SH_LOSS);
+  GNN_REQUIRE((labels != nullptr) == (loss != nullptr) && (!labels || counts),
+              "gnn_eval_step: labels, loss and counts come together (all NULL: predict)");
+  GNN_REQUIRE(labels || logits, "gnn_eval_step: nothing to produce (no labels, no logits)");
+  Arena ar{(char*)workspace};
+  Run r;
+  Plan& pl = r.pl;
+  {
+    Arena dry{nullptr};
+    Plan tmp;
+    GNN_TRY(plan_eval(d, dry, tmp));
+    GNN_TRY(check_workspace(workspace, workspace_bytes, dry.off));
+    GNN_REQUIRE((!logits || ldz >= tmp.C) && (!labels || d[GNN_SH_LDL] >= tmp.C),
+                "gnn_eval_step: logits / labels row stride below %lld classes", (long long)tmp.C);
+  }
+  GNN_TRY(plan_eval(d, ar, pl));
+  GNN_TRY(r.open(d, (hipStream_t)stream));
+  GNN_TRY(forward(r));  // training = 0, no timing records, phase 0
+  const LayerBufs& top = pl.lb[pl.nl - 1];
+  return gnn_head_eval_f32(top.Y, top.D, pl.Mh, pl.Dh, HP<const float>(d, GNN_SH_HEAD_W),
+                           HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, d[GNN_SH_LDL], logits, ldz, pl.rowloss,
+                           pl.rowmask, loss, counts, mode, stream);
 }
 
 }  // extern "C"

@@ -43,7 +43,10 @@ def enabled() -> bool:
 class NativeStep:
     """Binds a fused ``models.GNN`` (GraphSage or GCN encoder, every layer of order 1) to
     gnn_train_step_f32. ``step(x0, adjs, sampled_nodes, labels)`` runs forward + backward and
-    returns the loss (a device scalar); the gradients are in the parameters' ``.grad``."""
+    returns the loss (a device scalar); the gradients are in the parameters' ``.grad``.
+    ``evaluate(x0, adjs, sampled_nodes, labels)`` runs the forward alone through
+    gnn_eval_step_f32 for validation / test batches (main.py:178-199, 217-241): loss, per-class
+    prediction counts and, on request, logits — the same parameters, no gradient touched."""
 
     def __init__(self, model):
         from . import models
@@ -102,26 +105,33 @@ class NativeStep:
                 raise ValueError("NativeStep: parameters must be contiguous float32 CUDA tensors")
         self.template = d
 
-    def supports(self, x0, adjs, sampled_nodes, labels) -> bool:
-        """Whether this batch fits the executor (CSR operands with their transposes, row maps)."""
+    def supports(self, x0, adjs, sampled_nodes, labels, inference: bool = False) -> bool:
+        """Whether this batch fits the executor (CSR operands with their transposes, row maps).
+        inference=True: for ``evaluate`` — a forward needs neither transposes nor row maps, and
+        ``labels`` may be None (predict)."""
         from .custom_sparse_ops import CsrOperand
 
-        if not (x0.is_cuda and x0.dtype == torch.float32 and x0.stride(1) == 1 and labels.dtype == torch.float32
-                and labels.dim() == 2 and labels.stride(1) == 1):
+        if not (x0.is_cuda and x0.dtype == torch.float32 and x0.stride(1) == 1):
             return False
         C, D = self.model.linear.weight.shape
-        if C > 256 or D % 4 or D > 2048 or labels.shape[1] != C:  # the fused head's contract (fused.head_supported)
+        if C > 256 or D % 4 or D > 2048:  # the fused head's contract (fused.head_supported)
+            return False
+        if labels is None:
+            if not inference:
+                return False
+        elif not (labels.dtype == torch.float32 and labels.dim() == 2 and labels.stride(1) == 1
+                  and labels.shape[1] == C):
             return False
         for li, op in enumerate(adjs):
             if not isinstance(op, CsrOperand):
                 return False
-            if li >= 1 and op._t is None:
+            if li >= 1 and op._t is None and not inference:
                 return False
             if self.kind == SAGE:
                 s = sampled_nodes[li]
                 if s.dtype != torch.int64 or not s.is_contiguous() or s.numel() != op.shape[0]:
                     return False
-                if li >= 1 and getattr(s, "_gnn_rmap", None) is None:
+                if li >= 1 and getattr(s, "_gnn_rmap", None) is None and not inference:
                     return False
         return True
 
@@ -219,13 +229,41 @@ class NativeStep:
             p.grad = gr
         return loss
 
-    def _desc(self, x0, adjs, sampled_nodes, labels, seeds: bool):
+    def evaluate(self, x0, adjs, sampled_nodes, labels=None, mode: int = 0, want_logits: bool = False):
+        """Forward only (gnn_eval_step_f32: no dropout whatever the model's mode, no backward, no
+        gradient buffer touched) with the fused evaluation head. Returns (loss, counts, logits),
+        device tensors, nothing synchronised: loss a scalar and counts int32 [3, C] = per-class
+        (tp, fp, fn) of this batch (gnn_amd.metrics; mode 0 sigmoid, 1 argmax) — both None
+        without labels (predict, which always returns the logits); logits [M, C] or None."""
+        want_logits = want_logits or labels is None
+        d = self._desc(x0, adjs, sampled_nodes, labels, seeds=False, forward_only=True)
+        dev = x0.device
+        C = int(d[H_CLASSES])
+        loss = counts = logits = None
+        if labels is not None:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            counts = torch.empty((3, C), dtype=torch.int32, device=dev)
+            d[H_LOSS] = loss.data_ptr()
+        if want_logits:
+            logits = torch.empty((adjs[-1].shape[0], C), dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        wsb = L.gnn_eval_step_workspace_bytes(d.ctypes.data)
+        if wsb == 0:
+            raise RuntimeError("gnn_eval_step_workspace_bytes: " + L.gnn_last_error().decode(errors="replace"))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(L.gnn_eval_step_f32(d.ctypes.data, _p(logits), C, _p(counts), int(mode), ws.data_ptr(), wsb,
+                                           _lib.stream_of(dev)), "gnn_eval_step_f32")
+        return loss, counts, logits
+
+    def _desc(self, x0, adjs, sampled_nodes, labels, seeds: bool, forward_only: bool = False):
         model = self.model
-        training = model.training
+        training = model.training and not forward_only
         tr = bool(training and self.p_enc > 0)
         d = self.template.copy()
         d[H_X0], d[H_LDX0], d[H_F0] = x0.data_ptr(), x0.stride(0) if x0.shape[0] > 1 else x0.shape[1], x0.shape[1]
-        d[H_LABELS], d[H_LDL] = labels.data_ptr(), labels.stride(0) if labels.shape[0] > 1 else labels.shape[1]
+        if labels is not None:
+            d[H_LABELS], d[H_LDL] = labels.data_ptr(), labels.stride(0) if labels.shape[0] > 1 else labels.shape[1]
         d[H_TRAINING] = int(tr)
         # the Python path draws one seed per layer tail, then one for the head (fused.py): one
         # randint call for all of them gives the same values from the CPU generator (one call
@@ -235,7 +273,7 @@ class NativeStep:
             b = HEADER + li * LAYER_SLOTS
             d[b + L_ROWPTR], d[b + L_COL], d[b + L_VAL] = op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr()
             d[b + L_M], d[b + L_K], d[b + L_NNZ] = op.shape[0], op.shape[1], op.nnz
-            if li >= 1:
+            if li >= 1 and not forward_only:
                 t = op._t
                 d[b + L_TROWPTR], d[b + L_TCOL], d[b + L_TVAL] = t.rowptr.data_ptr(), t.col.data_ptr(), t.val.data_ptr()
             if self.kind == SAGE:

@@ -63,6 +63,17 @@ def prepare_data(pool, sampler_fn, target_nodes, samp_num_list, num_nodes, lap_m
         raise ValueError(f"unknown mode {mode!r}")
 
 
+def sequential_chunks(nodes, batch_size: int):
+    """Consecutive chunks of ``nodes`` in order, the last one short."""
+    nodes = np.asarray(nodes)
+    if batch_size <= 0:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    return [nodes[i:i + batch_size] for i in range(0, len(nodes), batch_size)]
+
+
+EVAL_SEED_OFFSET = 104729  # sequential()'s sampler seeds: a stream apart from the training one
+
+
 @dataclass
 class LoadedBatch:
     host: smp.HostBatch
@@ -109,6 +120,7 @@ class BatchLoader:
         self.workers = max(1, int(workers))
         self.prefetch = prefetch if prefetch > 0 else 2 * self.workers
         self.rng = np.random.RandomState(seed + 7919 * rank)
+        self.eval_seed = seed + 7919 * rank + EVAL_SEED_OFFSET
         self.skewed = skewed_sampling_nodes
         self.scale_factor = float(scale_factor)
         self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="gnn-sampler")
@@ -132,7 +144,17 @@ class BatchLoader:
                 e += 1
         return self._stream(chunks())
 
-    def _stream(self, chunks) -> Iterator[LoadedBatch]:
+    def sequential(self, nodes, batch_size: Optional[int] = None) -> Iterator[LoadedBatch]:
+        """Ordered stream over fixed consecutive chunks of ``nodes`` — no permutation, the last
+        chunk short — for validation and test passes (what prepare_data(mode="test") intends,
+        sampler.py:197-204). Produced, pinned and staged like training batches. The sampler seeds
+        come from a generator of this call's own, so the training stream's draws (``epoch``,
+        ``forever``) are the same whether or not an evaluation ran in between."""
+        return self._stream(sequential_chunks(nodes, batch_size or self.batch_size),
+                            np.random.RandomState(self.eval_seed))
+
+    def _stream(self, chunks, rng=None) -> Iterator[LoadedBatch]:
+        rng = self.rng if rng is None else rng
         q = collections.deque()
         it = iter(chunks)
         done = False
@@ -143,7 +165,7 @@ class BatchLoader:
                 except StopIteration:
                     done = True
                     break
-                q.append(self.pool.submit(self._produce, int(self.rng.randint(2**32 - 1)), nodes))
+                q.append(self.pool.submit(self._produce, int(rng.randint(2**32 - 1)), nodes))
             if not q:
                 return
             yield q.popleft().result()
@@ -498,6 +520,7 @@ class NativeLoader:
         self.workers = max(1, int(workers))
         self.prefetch = prefetch if prefetch > 0 else 2 * self.workers
         self.rng = np.random.RandomState(seed + 7919 * rank)
+        self.eval_seed = seed + 7919 * rank + EVAL_SEED_OFFSET
         lab = sp.csr_matrix(labels_full)
         nl = len(orders)
         # borrowed by the C++ loader: kept alive here
@@ -550,11 +573,11 @@ class NativeLoader:
                 self.device_count_workers = k
         self._pending = 0
 
-    def _submit(self, nodes) -> None:
+    def _submit(self, nodes, rng=None) -> None:
         from . import _lib
 
         nodes = np.ascontiguousarray(nodes, dtype=np.int64)
-        seed = int(self.rng.randint(2**32 - 1))
+        seed = int((self.rng if rng is None else rng).randint(2**32 - 1))
         _lib.check_sampler(_lib.sampler_lib().gnn_loader_submit(self.handle, seed, nodes.ctypes.data, nodes.size),
                            "gnn_loader_submit")
         self._pending += 1
@@ -580,13 +603,26 @@ class NativeLoader:
                 e += 1
         return self._stream(chunks())
 
-    def _stream(self, chunks) -> Iterator[LoadedBatch]:
+    def sequential(self, nodes, batch_size: Optional[int] = None) -> Iterator[LoadedBatch]:
+        """BatchLoader.sequential on the C++ workers: consecutive chunks of ``nodes`` in order, the
+        last one short, seeds from a generator of the call's own (the training stream's draws are
+        unchanged). The workers hand batches out in submission order from one queue, so drain a
+        training stream (an ``epoch``) before iterating this one."""
+        def checked():
+            if self._pending:
+                raise RuntimeError("NativeLoader.sequential: another stream still has batches in flight")
+            yield from self._stream(sequential_chunks(nodes, batch_size or self.batch_size),
+                                    np.random.RandomState(self.eval_seed))
+        return checked()
+
+    def _stream(self, chunks, rng=None) -> Iterator[LoadedBatch]:
+        rng = self.rng if rng is None else rng
         it = iter(chunks)
         done = False
         while True:
             while not done and self._pending < self.prefetch:
                 try:
-                    self._submit(next(it))
+                    self._submit(next(it), rng)
                 except StopIteration:
                     done = True
             if self._pending == 0:

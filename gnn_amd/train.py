@@ -209,6 +209,127 @@ class Trainer:
         return loss.detach()
 
 
+    def evaluate(self, batches, mode: Optional[int] = None) -> dict:
+        """A validation / test pass (main.py:178-199, 217-241) over ``batches``, any iterable of
+        (x0, adjs, sampled_nodes, labels): the model in eval() (its previous mode is restored),
+        forward only through this trainer's executor where the batch allows it, one host
+        synchronisation at the end. mode: 0 sigmoid / multi-label, 1 argmax / single-label
+        (default: by ``sigmoid_loss``). Returns ``Evaluator.result()``."""
+        ev = Evaluator(self.model, self.device, self.sigmoid_loss, executor=self.executor, mode=mode)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            for x0, adjs, sampled_nodes, labels in batches:
+                ev.add(x0, adjs, sampled_nodes, labels)
+        finally:
+            self.model.train(was_training)
+        return ev.result()
+
+
+class Evaluator:
+    """Accumulates the loss and the per-class prediction counts of evaluation batches on the
+    device and turns them into F1 scores once, at ``result()``.
+
+    Reference: the validation block (main.py:178-199) and the test pass (main.py:217-241) pull
+    every batch's predictions and labels to the host for sklearn (utils.calc_f1), one stream
+    synchronisation per batch. Here a batch is one forward-only executor call
+    (NativeStep.evaluate: gnn_eval_step_f32 with the fused evaluation head) — or, for a model or
+    batch the executor does not take, ``model.forward_loss`` under no_grad and
+    metrics.prediction_counts — whose int32 counts [3, C] and loss land in one growing device
+    buffer; nothing is synchronised until ``result()`` copies that buffer to the host."""
+
+    def __init__(self, model, device, sigmoid_loss: bool = True, executor=None, mode: Optional[int] = None):
+        self.model = model
+        self.device = torch.device(device)
+        self.sigmoid_loss = sigmoid_loss
+        self.mode = (0 if sigmoid_loss else 1) if mode is None else int(mode)
+        self.executor = executor
+        self.rows = []  # per batch, known on the host
+        self._buf = None  # int32 [capacity, 3 C + 1]: a batch's counts, then its loss's bits
+        self.native_batches = 0
+
+    def _native(self, x0, adjs, sampled_nodes, labels) -> bool:
+        # the executor's loss is the BCE-with-logits one
+        return (self.executor is not None and (labels is None or self.sigmoid_loss)
+                and self.executor.supports(x0, adjs, sampled_nodes, labels, inference=True))
+
+    def _eval_mode(self):
+        """The model in eval() for one fallback forward; returns whether to switch it back."""
+        was_training = self.model.training
+        if was_training:
+            self.model.eval()
+        return was_training
+
+    def add(self, x0, adjs, sampled_nodes, labels):
+        """One batch. Returns its (loss, counts) as device tensors; synchronises nothing."""
+        from . import metrics
+
+        if self._native(x0, adjs, sampled_nodes, labels):
+            loss, counts, _ = self.executor.evaluate(x0, adjs, sampled_nodes, labels, mode=self.mode)
+            self.native_batches += 1
+        else:
+            was_training = self._eval_mode()
+            try:
+                with torch.no_grad():
+                    if hasattr(self.model, "forward_loss"):
+                        loss, out = self.model.forward_loss(x0, adjs, sampled_nodes, labels, self.sigmoid_loss)
+                    else:
+                        out = self.model(x0, adjs, sampled_nodes)
+                        loss = loss_fn(out, labels, self.sigmoid_loss, out.device)
+            finally:
+                if was_training:
+                    self.model.train()
+            loss = loss.detach().to(torch.float32)
+            counts = metrics.prediction_counts(out, labels, self.mode)
+        n, width = len(self.rows), counts.numel() + 1
+        if self._buf is None or n == self._buf.shape[0]:
+            grown = torch.empty((max(16, 2 * n), width), dtype=torch.int32, device=counts.device)
+            if n:
+                grown[:n] = self._buf
+            self._buf = grown
+        self._buf[n, :width - 1] = counts.reshape(-1)
+        self._buf[n, width - 1:] = loss.reshape(1).view(torch.int32)
+        self.rows.append(int(labels.shape[0]))
+        return loss, counts
+
+    def predict(self, x0, adjs, sampled_nodes) -> torch.Tensor:
+        """The logits [M, C] of one batch (model.eval(), no dropout), on the device."""
+        if self._native(x0, adjs, sampled_nodes, None):
+            return self.executor.evaluate(x0, adjs, sampled_nodes, None)[2]
+        was_training = self._eval_mode()
+        try:
+            with torch.no_grad():
+                return self.model(x0, adjs, sampled_nodes)
+        finally:
+            if was_training:
+                self.model.train()
+
+    def result(self) -> dict:
+        """One device-to-host copy, then: ``micro_f1`` / ``macro_f1`` of the counts summed over the
+        batches (the scores of the whole pass), ``loss`` (mean over rows), ``batches``, ``rows``,
+        and ``ref_batch_weighted_micro_f1`` = Σ_b micro_b rows_b / Σ_b rows_b, the number the
+        reference's test pass prints (main.py:237-241)."""
+        from . import metrics
+
+        n = len(self.rows)
+        if n == 0:
+            return {"micro_f1": 0.0, "macro_f1": 0.0, "loss": 0.0, "batches": 0, "rows": 0,
+                    "ref_batch_weighted_micro_f1": 0.0}
+        host = self._buf[:n].cpu()
+        counts = host[:, :-1].reshape(n, 3, -1).numpy().astype("int64")
+        losses = host[:, -1:].contiguous().view(torch.float32).reshape(n).double().numpy()
+        rows = [float(r) for r in self.rows]
+        total = sum(rows)
+        pooled = counts.sum(axis=0)
+        micro, macro = metrics.f1_from_counts(pooled[0], pooled[1], pooled[2], self.mode)
+        per_batch = [metrics.f1_from_counts(c[0], c[1], c[2], self.mode)[0] for c in counts]
+        return {"micro_f1": micro, "macro_f1": macro,
+                "loss": float(sum(l * r for l, r in zip(losses, rows)) / total) if total else 0.0,
+                "batches": n, "rows": int(total),
+                "ref_batch_weighted_micro_f1": float(sum(m * r for m, r in zip(per_batch, rows)) / total)
+                if total else 0.0}
+
+
 DEFAULT_TIMEOUT_S = 180.0
 
 

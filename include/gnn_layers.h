@@ -134,6 +134,32 @@ int gnn_head_bce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, cons
                          int training, const float* z, const float* norm, float* dz, float* dX, int64_t lddx,
                          void* stream);
 
+/* Evaluation head (head.hip): the forward above with training = 0 for a validation / test batch
+ * (main.py:178-199, 217-241: model.eval(), forward, utils.loss, utils.calc_f1) — no dropout, no
+ * xd / norm stores — plus the per-class prediction counts utils.calc_f1 (utils.py:142-149) feeds
+ * to sklearn's f1_score, so neither logits nor labels leave the device:
+ *   z (M x C, row stride ldz; NULL: not written): the same dot products in the same order as
+ *     gnn_head_bce_fwd_f32, bit-identical to its logits with training = 0;
+ *   *loss: the same terms and the same fixed-order row sum, bit-identical too;
+ *   counts[3][C] (int32, overwritten): tp, fp, fn per class over the M rows.
+ *     mode 0 (is_sigmoid = True):  pred_j = z_j > 0, true_j = y_j > 0.5 per class;
+ *     mode 1 (is_sigmoid = False): pred = argmax_j z_j, true = argmax_j y_j (the first index wins
+ *       ties, as np.argmax); tp[c] = #(pred = c and true = c), fp[c] = #(pred = c, true != c),
+ *       fn[c] = #(true = c, pred != c).
+ *     One deviation in mode 0: the reference thresholds sigmoid(z) > 0.5 computed in fp32, which
+ *     differs from z > 0 only for 0 < z < ~1.2e-7, where the fp32 sigmoid rounds to exactly 0.5
+ *     (there the reference predicts 0, this kernel 1).
+ * Two launches: the row pass leaves each row's loss terms in rowloss[M] and its predicted / true
+ * class sets as bit masks in rowmask[M][8] (uint64; words 0-3 predicted, 4-7 true); one workgroup
+ * per class then counts its bit over the rows (integers: exact and deterministic, no atomics)
+ * and one more sums the loss. labels NULL: only z is produced (predict); loss, counts, rowloss
+ * and rowmask are not touched and may be NULL. M = 0 launches no row pass and writes zero counts
+ * and a zero loss. Contract as gnn_head_bce_fwd_f32: D % 4 == 0, D <= 2048, C <= 256, X and W
+ * 16-byte aligned, ldx % 4 == 0. */
+int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                      int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
+                      uint64_t* rowmask, float* loss, int32_t* counts, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

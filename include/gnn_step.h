@@ -78,6 +78,25 @@ enum {
 size_t gnn_train_step_workspace_bytes(const int64_t* desc);
 int gnn_train_step_f32(const int64_t* desc, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Forward-only step for validation / test batches (main.py:178-199, 217-241: model.eval(), the
+ * same staging and forward, utils.loss, utils.calc_f1): the training step's forward with
+ * training = 0 — the same kernels with the same routing, issued by the same code — and then the
+ * evaluation head (gnn_head_eval_f32, gnn_layers.h): the loss, the logits (M_top x C, row stride
+ * ldz; NULL: not written) and the per-class prediction counts[3][C] (tp, fp, fn; int32,
+ * overwritten; mode 0: sigmoid / multi-label, 1: argmax / single-label).
+ * Takes the same version-1 descriptor and reads only what a forward needs: gradient pointers,
+ * transposes (GNN_SL_T*), GNN_SL_RMAP, the seeds, GNN_SH_TRAINING, GNN_SH_TIMING and
+ * GNN_SH_GRAD_EVENTS are ignored and may be 0; GNN_SH_PHASE must be 0; GNN_SH_STAGE_EVENT is
+ * honoured as in training. GNN_SH_LABELS and GNN_SH_LOSS may be 0 together (predict: only the
+ * logits; counts may be NULL). The loss equals, bit for bit, what gnn_train_step_f32 writes for
+ * the same descriptor with training = 0.
+ * The workspace holds no backward buffer and one set of forward buffers shared by all layers:
+ * gnn_eval_step_workspace_bytes(desc) < gnn_train_step_workspace_bytes(desc) for every valid
+ * descriptor. It is validated (size, 256-byte alignment) before anything is launched. */
+size_t gnn_eval_step_workspace_bytes(const int64_t* desc);
+int gnn_eval_step_f32(const int64_t* desc, float* logits, int64_t ldz, int32_t* counts, int mode, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
