@@ -86,6 +86,12 @@ _SIGNATURES = {
                                     ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _I64, _VP]),
     "gnn_head_eval_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _INT,
                                  _VP]),
+    "gnn_head_ce_fwd_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, ctypes.c_float,
+                                   ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gnn_head_ce_bwd_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, ctypes.c_float,
+                                   ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "gnn_head_eval_loss_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP,
+                                      _INT, _INT, _VP]),
     # include/gnn_extract.h
     "gnn_ladies_extract_workspace_bytes": (_SZ, [_I64, _I64, _I64, ctypes.c_int32, _I64, _I64]),
     "gnn_colcount_create": (_INT, [ctypes.c_int32, _I64, _VP, _VP, ctypes.POINTER(_VP)]),

@@ -14,6 +14,12 @@
 // same row pass without dropout and without the xd store, and leaves each row's predicted and
 // true class sets as 64-bit ballot masks; one workgroup per class then counts tp / fp / fn over
 // the rows (gnn_head_eval_f32): logits and labels never travel to the host for sklearn.
+//
+// The softmax cross-entropy loss (utils.py:138-140, sigmoid_loss = False: CrossEntropyLoss(
+// reduction = "none") over float target rows, weighted 1/M and summed) is the same three kernels
+// instantiated with LOSS = 1 (gnn_head_ce_*, gnn_head_eval_loss_f32): the row pass is shared, so
+// the logits, the dropped-out row and the norm are those of the BCE head bit for bit; wave 0 adds
+// the row's log-sum-exp (kept for the backward) and the terms y_j (lse - z_j).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -168,34 +174,77 @@ __device__ __forceinline__ float bce_term(float z, float y) {
   return fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
 }
 
-template <int PV>
+constexpr int LOSS_BCE = 0, LOSS_CE = 1;  // GNN_LOSS_* (gnn_step.h)
+
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmaxf(x, __shfl_xor(x, m));
+  return x;
+}
+
+// Softmax cross-entropy of one row on one wave: lane holds the logits z[q] and the targets y[q]
+// of classes lane + 64 q (read only where the class is < C). Returns lse = m + log Σ_j exp(z_j - m)
+// (m the row maximum) and, in term, this lane's share of Σ_j y_j (lse - z_j): subtracted per
+// class — lse Σy - Σ y z cancels catastrophically for logits near ±200. Targets are
+// probabilities as in torch (they need not sum to 1; an all-zero row gives 0).
+__device__ __forceinline__ float ce_row(const float (&z)[HEAD_CQ], const float (&y)[HEAD_CQ], int lane, int C,
+                                        float& term) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < HEAD_CQ; ++q)
+    if (lane + 64 * q < C) m = fmaxf(m, z[q]);
+  m = wave_max(m);
+  float s = 0.0f;
+#pragma unroll
+  for (int q = 0; q < HEAD_CQ; ++q)
+    if (lane + 64 * q < C) s += expf(z[q] - m);
+  const float lse = m + logf(wave_sum(s));
+  term = 0.0f;
+#pragma unroll
+  for (int q = 0; q < HEAD_CQ; ++q)
+    if (lane + 64 * q < C) term = fmaf(y[q], lse - z[q], term);
+  return lse;
+}
+
+// LOSS: LOSS_BCE or LOSS_CE (lse[M] is written by LOSS_CE only)
+template <int PV, int LOSS>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
                                                        const float* __restrict__ W, const float* __restrict__ bias,
                                                        int C, const float* __restrict__ Y, int64_t ldy_lab,
                                                        float row_weight, float p, uint64_t seed, int training,
                                                        float* __restrict__ XD, float* __restrict__ Z,
-                                                       float* __restrict__ nrm, float* __restrict__ rowloss) {
+                                                       float* __restrict__ nrm, float* __restrict__ rowloss,
+                                                       float* __restrict__ lse) {
   __shared__ float part[WPR][HEAD_MAXC + 1];  // [w][j] class partials, [w][HEAD_MAXC] sum of squares
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = blockIdx.x;
   const bool tr = training != 0 && p > 0.0f;
   const float norm = head_row_partials<PV, true>(X, ldx, r, D, W, C, p, seed, tr, XD, part);
   if (w != 0) return;
-  // lane j: logits j, j + 64, ... and their BCE terms
+  // lane j: logits j, j + 64, ... and their loss terms
   float term = 0.0f;
+  float zq[HEAD_CQ], yq[HEAD_CQ];  // LOSS_CE: the row's logits and targets, for the second pass
 #pragma unroll
   for (int q = 0; q < HEAD_CQ; ++q) {
     const int j = lane + 64 * q;
     if (j < C) {
       const float z = head_logit(part, j, bias);
       Z[(int64_t)r * C + j] = z;
-      term += bce_term(z, Y[(int64_t)r * ldy_lab + j]);
+      if constexpr (LOSS == LOSS_BCE) {
+        term += bce_term(z, Y[(int64_t)r * ldy_lab + j]);
+      } else {
+        zq[q] = z;
+        yq[q] = Y[(int64_t)r * ldy_lab + j];
+      }
     }
   }
+  float row_lse = 0.0f;
+  if constexpr (LOSS == LOSS_CE) row_lse = ce_row(zq, yq, lane, C, term);
   const float loss = wave_sum(term);
   if (lane == 0) {
     nrm[r] = norm;
     rowloss[r] = loss * row_weight;
+    if constexpr (LOSS == LOSS_CE) lse[r] = row_lse;
   }
 }
 
@@ -217,8 +266,9 @@ __device__ __forceinline__ int wave_argmax(float v, int i) {
 // without the xd / norm stores; logits to Z (row stride ldz) when Z is given; with labels, the
 // row's loss terms and its predicted / true class sets as bit masks: rowmask[r][q] (q < 4) bit b
 // = class 64 q + b predicted, rowmask[r][4 + q] = class 64 q + b true. mode 0: z > 0 / y > 0.5
-// per class; mode 1: the one-hot argmax of the logits / of the labels.
-template <int PV>
+// per class; mode 1: the one-hot argmax of the logits / of the labels. LOSS picks the row's loss
+// terms (LOSS_BCE / LOSS_CE), independently of mode.
+template <int PV, int LOSS>
 __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
                                                         const float* __restrict__ W, const float* __restrict__ bias,
                                                         int C, const float* __restrict__ Y, int64_t ldy_lab,
@@ -230,6 +280,7 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict_
   const int r = blockIdx.x;
   head_row_partials<PV, false>(X, ldx, r, D, W, C, 0.0f, 0, false, nullptr, part);
   if (w != 0) return;
+  float zq[HEAD_CQ], yq[HEAD_CQ];  // LOSS_CE: the row's logits and targets, for the second pass
   float term = 0.0f, bz = -INFINITY, by = -INFINITY;
   int zi = INT_MAX, yi = INT_MAX;
   bool pj[HEAD_CQ], tj[HEAD_CQ];
@@ -242,7 +293,12 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict_
       if (Z) Z[(int64_t)r * ldz + j] = z;
       if (Y) {
         const float y = Y[(int64_t)r * ldy_lab + j];
-        term += bce_term(z, y);
+        if constexpr (LOSS == LOSS_BCE) {
+          term += bce_term(z, y);
+        } else {
+          zq[q] = z;
+          yq[q] = y;
+        }
         pj[q] = z > 0.0f;
         tj[q] = y > 0.5f;
         if (z > bz) bz = z, zi = j;  // ascending j per lane: the first of equal values stays
@@ -266,6 +322,7 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict_
     pm[q] = __ballot(pj[q]);
     tm[q] = __ballot(tj[q]);
   }
+  if constexpr (LOSS == LOSS_CE) ce_row(zq, yq, lane, C, term);
   const float loss = wave_sum(term);
   if (lane == 0) {
     rowloss[r] = loss * row_weight;
@@ -328,30 +385,44 @@ __global__ __launch_bounds__(256) void head_eval_reduce_kernel(const float* __re
   }
 }
 
-template <int PV>
+template <int PV, int LOSS>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ X, int64_t ldx, int M, int D,
                                                        const float* __restrict__ W, int C,
                                                        const float* __restrict__ Y, int64_t ldy_lab,
                                                        float row_weight, const float* __restrict__ gloss, float p,
                                                        uint64_t seed, int training, const float* __restrict__ Z,
                                                        const float* __restrict__ nrm, float* __restrict__ DZ,
-                                                       float* __restrict__ DX, int64_t lddx) {
+                                                       float* __restrict__ DX, int64_t lddx,
+                                                       const float* __restrict__ lse) {
   __shared__ float dots[WPR];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = blockIdx.x;
   const float inv_keep = 1.0f / (1.0f - p);
   const bool tr = training != 0 && p > 0.0f;
   const float g = gloss ? *gloss : 1.0f;
-  // dz_j = g * w * (sigmoid(z_j) - y_j), classes lane + 64 q per lane, in every wave
+  // classes lane + 64 q per lane, in every wave. LOSS_BCE: dz_j = g * w * (sigmoid(z_j) - y_j);
+  // LOSS_CE: dz_j = g * w * (softmax(z)_j Σ_k y_k - y_j), softmax(z)_j = exp(z_j - lse)
   float dz[HEAD_CQ];
+  float sy = 0.0f, row_lse = 0.0f;
+  if constexpr (LOSS == LOSS_CE) {
+#pragma unroll
+    for (int q = 0; q < HEAD_CQ; ++q)
+      if (lane + 64 * q < C) sy += Y[(int64_t)r * ldy_lab + lane + 64 * q];
+    sy = wave_sum(sy);
+    row_lse = lse[r];
+  }
 #pragma unroll
   for (int q = 0; q < HEAD_CQ; ++q) {
     const int j = lane + 64 * q;
     dz[q] = 0.0f;
     if (j < C) {
       const float z = Z[(int64_t)r * C + j];
-      const float sg = 1.0f / (1.0f + expf(-z));
-      dz[q] = g * row_weight * (sg - Y[(int64_t)r * ldy_lab + j]);
+      if constexpr (LOSS == LOSS_BCE) {
+        const float sg = 1.0f / (1.0f + expf(-z));
+        dz[q] = g * row_weight * (sg - Y[(int64_t)r * ldy_lab + j]);
+      } else {
+        dz[q] = g * row_weight * (expf(z - row_lse) * sy - Y[(int64_t)r * ldy_lab + j]);
+      }
       if (w == 0) DZ[(int64_t)r * C + j] = dz[q];
     }
   }
@@ -410,26 +481,24 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int gnn_head_bce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
-                         int64_t C, const float* labels, int64_t ldl, float p, uint64_t seed, int training,
-                         float* xd, float* z, float* norm, float* rowloss, float* loss, void* stream) {
-  GNN_REQUIRE(M >= 0 && D > 0 && C > 0, "gnn_head_bce_fwd_f32: bad sizes");
-  GNN_REQUIRE(D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV, "gnn_head_bce_fwd_f32: D must be a multiple of 4, <= %d",
-              64 * 4 * HEAD_MAXV);
-  GNN_REQUIRE(C <= HEAD_MAXC, "gnn_head_bce_fwd_f32: at most %d classes", HEAD_MAXC);
+// The forward of both losses (fn: the entry point's name, for the error text).
+int head_fwd(const char* fn, int loss_kind, const float* X, int64_t ldx, int64_t M, int64_t D, const float* W,
+             const float* bias, int64_t C, const float* labels, int64_t ldl, float p, uint64_t seed, int training,
+             float* xd, float* z, float* norm, float* rowloss, float* lse, float* loss, void* stream) {
+  GNN_REQUIRE(M >= 0 && D > 0 && C > 0, "%s: bad sizes", fn);
+  GNN_REQUIRE(D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV, "%s: D must be a multiple of 4, <= %d", fn, 64 * 4 * HEAD_MAXV);
+  GNN_REQUIRE(C <= HEAD_MAXC, "%s: at most %d classes", fn, HEAD_MAXC);
   GNN_REQUIRE(ldx % 4 == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)W % 16 == 0 && (uintptr_t)xd % 16 == 0,
-              "gnn_head_bce_fwd_f32: X, W, xd must be 16-byte aligned with ldx % 4 == 0");
-  GNN_REQUIRE(M < INT_MAX && p >= 0.0f && p < 1.0f, "gnn_head_bce_fwd_f32: bad M or p");
-  GNN_REQUIRE(loss && rowloss && z && norm && labels, "gnn_head_bce_fwd_f32: NULL output");
+              "%s: X, W, xd must be 16-byte aligned with ldx %% 4 == 0", fn);
+  GNN_REQUIRE(M < INT_MAX && p >= 0.0f && p < 1.0f, "%s: bad M or p", fn);
+  GNN_REQUIRE(loss && rowloss && z && norm && labels && (lse || loss_kind != LOSS_CE), "%s: NULL output", fn);
   hipStream_t st = (hipStream_t)stream;
   if (M > 0) {
-    auto k = D <= 64 * 4 * WPR ? head_fwd_kernel<1> : head_fwd_kernel<2>;
+    const bool one = D <= 64 * 4 * WPR;
+    auto k = loss_kind == LOSS_CE ? (one ? head_fwd_kernel<1, LOSS_CE> : head_fwd_kernel<2, LOSS_CE>)
+                                  : (one ? head_fwd_kernel<1, LOSS_BCE> : head_fwd_kernel<2, LOSS_BCE>);
     k<<<dim3((unsigned)M), dim3(64 * WPR), 0, st>>>(X, ldx, (int)M, (int)D, W, bias, (int)C, labels, ldl,
-                                                    1.0f / (float)M, p, seed, training, xd, z, norm, rowloss);
+                                                    1.0f / (float)M, p, seed, training, xd, z, norm, rowloss, lse);
     GNN_LAUNCHED("head_fwd_kernel");
   }
   head_loss_sum_kernel<<<dim3(1), dim3(256), 0, st>>>(rowloss, (int)M, loss);
@@ -437,9 +506,47 @@ int gnn_head_bce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, cons
   return 0;
 }
 
-int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
-                      int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
-                      uint64_t* rowmask, float* loss, int32_t* counts, int mode, void* stream) {
+int head_bwd(const char* fn, int loss_kind, const float* X, int64_t ldx, int64_t M, int64_t D, const float* W,
+             int64_t C, const float* labels, int64_t ldl, const float* grad_loss, float p, uint64_t seed,
+             int training, const float* z, const float* norm, const float* lse, float* dz, float* dX, int64_t lddx,
+             void* stream) {
+  GNN_REQUIRE(M >= 0 && D > 0 && C > 0 && C <= HEAD_MAXC && D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV, "%s: bad sizes",
+              fn);
+  GNN_REQUIRE(lddx % 4 == 0 && (uintptr_t)dX % 16 == 0 && ldx % 4 == 0 && (uintptr_t)X % 16 == 0,
+              "%s: X / dX must be 16-byte aligned", fn);
+  GNN_REQUIRE(lse || loss_kind != LOSS_CE, "%s: NULL lse", fn);
+  if (M == 0) return 0;
+  const bool one = D <= 64 * 4 * WPR;
+  auto k = loss_kind == LOSS_CE ? (one ? head_bwd_kernel<1, LOSS_CE> : head_bwd_kernel<2, LOSS_CE>)
+                                : (one ? head_bwd_kernel<1, LOSS_BCE> : head_bwd_kernel<2, LOSS_BCE>);
+  k<<<dim3((unsigned)M), dim3(64 * WPR), 0, (hipStream_t)stream>>>(
+      X, ldx, (int)M, (int)D, W, (int)C, labels, ldl, 1.0f / (float)M, grad_loss, p, seed, training, z, norm, dz,
+      dX, lddx, lse);
+  GNN_LAUNCHED("head_bwd_kernel");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnn_head_bce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                         int64_t C, const float* labels, int64_t ldl, float p, uint64_t seed, int training,
+                         float* xd, float* z, float* norm, float* rowloss, float* loss, void* stream) {
+  return head_fwd("gnn_head_bce_fwd_f32", LOSS_BCE, X, ldx, M, D, W, bias, C, labels, ldl, p, seed, training, xd, z,
+                  norm, rowloss, nullptr, loss, stream);
+}
+
+int gnn_head_ce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                        int64_t C, const float* labels, int64_t ldl, float p, uint64_t seed, int training, float* xd,
+                        float* z, float* norm, float* rowloss, float* loss, float* lse, void* stream) {
+  return head_fwd("gnn_head_ce_fwd_f32", LOSS_CE, X, ldx, M, D, W, bias, C, labels, ldl, p, seed, training, xd, z,
+                  norm, rowloss, lse, loss, stream);
+}
+
+int gnn_head_eval_loss_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                           int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
+                           uint64_t* rowmask, float* loss, int32_t* counts, int mode, int loss_kind, void* stream) {
   GNN_REQUIRE(M >= 0 && D > 0 && C > 0, "gnn_head_eval_f32: bad sizes");
   GNN_REQUIRE(D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV, "gnn_head_eval_f32: D must be a multiple of 4, <= %d",
               64 * 4 * HEAD_MAXV);
@@ -447,6 +554,8 @@ int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const f
   GNN_REQUIRE(ldx % 4 == 0 && ldx >= D && (uintptr_t)X % 16 == 0 && (uintptr_t)W % 16 == 0,
               "gnn_head_eval_f32: X, W must be 16-byte aligned with ldx % 4 == 0, ldx >= D");
   GNN_REQUIRE(M < INT_MAX && (mode == 0 || mode == 1), "gnn_head_eval_f32: bad M or mode %d", mode);
+  GNN_REQUIRE(loss_kind == LOSS_BCE || loss_kind == LOSS_CE, "gnn_head_eval_loss_f32: loss kind %d (0: BCE, 1: CE)",
+              loss_kind);
   GNN_REQUIRE(!z || ldz >= C, "gnn_head_eval_f32: ldz < C");
   // the loss and the counts come with labels (an empty batch still zeroes them)
   const bool scored = labels != nullptr || (M == 0 && loss != nullptr);
@@ -455,7 +564,9 @@ int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const f
                 "gnn_head_eval_f32: labels need loss, counts, rowloss, rowmask and ldl >= C");
   hipStream_t st = (hipStream_t)stream;
   if (M > 0 && (scored || z)) {
-    auto k = D <= 64 * 4 * WPR ? head_eval_kernel<1> : head_eval_kernel<2>;
+    const bool one = D <= 64 * 4 * WPR;
+    auto k = loss_kind == LOSS_CE ? (one ? head_eval_kernel<1, LOSS_CE> : head_eval_kernel<2, LOSS_CE>)
+                                  : (one ? head_eval_kernel<1, LOSS_BCE> : head_eval_kernel<2, LOSS_BCE>);
     k<<<dim3((unsigned)M), dim3(64 * WPR), 0, st>>>(X, ldx, (int)M, (int)D, W, bias, (int)C, labels, ldl,
                                                     1.0f / (float)M, mode, z, ldz, rowloss,
                                                     (unsigned long long*)rowmask);
@@ -469,21 +580,27 @@ int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const f
   return 0;
 }
 
+int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                      int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
+                      uint64_t* rowmask, float* loss, int32_t* counts, int mode, void* stream) {
+  return gnn_head_eval_loss_f32(X, ldx, M, D, W, bias, C, labels, ldl, z, ldz, rowloss, rowmask, loss, counts, mode,
+                                LOSS_BCE, stream);
+}
+
 int gnn_head_bce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, int64_t C,
                          const float* labels, int64_t ldl, const float* grad_loss, float p, uint64_t seed,
                          int training, const float* z, const float* norm, float* dz, float* dX, int64_t lddx,
                          void* stream) {
-  GNN_REQUIRE(M >= 0 && D > 0 && C > 0 && C <= HEAD_MAXC && D % 4 == 0 && D <= 64 * 4 * HEAD_MAXV,
-              "gnn_head_bce_bwd_f32: bad sizes");
-  GNN_REQUIRE(lddx % 4 == 0 && (uintptr_t)dX % 16 == 0 && ldx % 4 == 0 && (uintptr_t)X % 16 == 0,
-              "gnn_head_bce_bwd_f32: X / dX must be 16-byte aligned");
-  if (M == 0) return 0;
-  auto k = D <= 64 * 4 * WPR ? head_bwd_kernel<1> : head_bwd_kernel<2>;
-  k<<<dim3((unsigned)M), dim3(64 * WPR), 0, (hipStream_t)stream>>>(
-      X, ldx, (int)M, (int)D, W, (int)C, labels, ldl, 1.0f / (float)M, grad_loss, p, seed, training, z, norm, dz,
-      dX, lddx);
-  GNN_LAUNCHED("head_bwd_kernel");
-  return 0;
+  return head_bwd("gnn_head_bce_bwd_f32", LOSS_BCE, X, ldx, M, D, W, C, labels, ldl, grad_loss, p, seed, training, z,
+                  norm, nullptr, dz, dX, lddx, stream);
+}
+
+int gnn_head_ce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, int64_t C,
+                        const float* labels, int64_t ldl, const float* grad_loss, float p, uint64_t seed, int training,
+                        const float* z, const float* norm, float* dz, float* dX, int64_t lddx, const float* lse,
+                        void* stream) {
+  return head_bwd("gnn_head_ce_bwd_f32", LOSS_CE, X, ldx, M, D, W, C, labels, ldl, grad_loss, p, seed, training, z,
+                  norm, lse, dz, dX, lddx, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 //
 // Reference (main.py:122-146): output = model(x0, adjs, sampled_nodes); loss = utils.loss(...);
 // loss.backward() — GraphSageConvolution / GraphConvolution (models.py:6-64) per layer, GNN's
-// head (models.py:86-97) and the BCE loss (utils.py:129-140), autograd for the backward.
+// head (models.py:86-97) and the loss (utils.py:129-140: BCE with logits, or softmax cross-entropy
+// for GNN_SH_LOSS_KIND = GNN_LOSS_CE), autograd for the backward.
 //
 // The Python path (gnn_amd.models fused=True) already runs every piece as a hand-written HIP
 // kernel, but through ~45 autograd Functions and ctypes calls per step: 1.2-1.5 ms of host time
@@ -19,7 +20,7 @@
 //   forward  l = 0..L-1:  feat = A_l·X (gnn_spmm_csr_f32);  [SAGE] xs = X[sampled] (row gather)
 //                         [hB,] hW = [xs, feat]·[W_B, W_W]ᵀ  (one batched split3 launch or rocBLAS)
 //                         Y_l = sage_norm(hB + b_B, hW + b_W)  (ELU, row standardise, scale/offset, dropout)
-//   head:                 loss, z = BCE(linear(dropout(normalize(Y_{L-1}))))
+//   head:                 loss, z = BCE or CE(linear(dropout(normalize(Y_{L-1}))))
 //   backward head:        dz, dY_{L-1};  dW_h = dzᵀ·xd (rocBLAS), db_h = colsum(dz)
 //   backward l = L-1..0:  dhB, dhW, dscale, doffset, dbB, dbW = sage_norm_bwd(dY_l)
 //                         dW_B, dW_W = [dhB, dhW]ᵀ·[xs, feat]  (split-k split3 from 2048 rows)
@@ -28,7 +29,7 @@
 //
 // gnn_eval_step_f32 (validation / test batches, main.py:178-199, 217-241) is the forward above
 // with training = 0 — forward() below, called by both entry points — followed by the evaluation
-// head (gnn_head_eval_f32: loss, logits, per-class prediction counts), on a plan without
+// head (gnn_head_eval_loss_f32: loss, logits, per-class prediction counts), on a plan without
 // backward buffers.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -251,7 +252,8 @@ struct LayerBufs {
 struct Plan {
   int nl = 0, sage = 1;
   LayerBufs lb[GNN_STEP_MAX_LAYERS];
-  float *xd, *z, *nrm, *rowloss, *dz, *dXh;
+  float *xd, *z, *nrm, *rowloss, *lse, *dz, *dXh;
+  int loss_kind = GNN_LOSS_BCE;
   uint64_t* rowmask;  // the evaluation head's per-row class masks (gnn_head_eval_f32)
   int64_t Mh = 0, Dh = 0, C = 0;
 };
@@ -267,6 +269,9 @@ struct Plan {
 int shapes(const int64_t* d, bool measuring, Plan& pl) {
   GNN_REQUIRE(d[GNN_SH_VERSION] == GNN_STEP_VERSION, "gnn_train_step: descriptor version %lld",
               (long long)d[GNN_SH_VERSION]);
+  GNN_REQUIRE(d[GNN_SH_LOSS_KIND] == GNN_LOSS_BCE || d[GNN_SH_LOSS_KIND] == GNN_LOSS_CE,
+              "gnn_train_step: loss kind %lld (0: BCE, 1: CE)", (long long)d[GNN_SH_LOSS_KIND]);
+  pl.loss_kind = (int)d[GNN_SH_LOSS_KIND];
   pl.nl = (int)d[GNN_SH_LAYERS];
   pl.sage = d[GNN_SH_KIND] == GNN_STEP_SAGE;
   GNN_REQUIRE(pl.nl >= 1 && pl.nl <= GNN_STEP_MAX_LAYERS, "gnn_train_step: %d layers", pl.nl);
@@ -373,6 +378,7 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
   pl.z = ar.take<float>(pl.Mh * pl.C);
   pl.nrm = ar.take<float>(pl.Mh);
   pl.rowloss = ar.take<float>(pl.Mh);
+  pl.lse = ar.take<float>(pl.Mh);  // the rows' log-sum-exp (GNN_LOSS_CE)
   pl.dz = ar.take<float>(pl.Mh * pl.C);
   pl.dXh = ar.take<float>(pl.Mh * pl.Dh);
   for (int l = pl.nl - 1; l >= 0; --l) {
@@ -620,11 +626,21 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
   const uint64_t hseed = (uint64_t)d[GNN_SH_HEAD_SEED];
   const float* labels = HP<const float>(d, GNN_SH_LABELS);
   const int64_t ldl = d[GNN_SH_LDL];
-  GNN_TRY(gnn_head_bce_fwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, ldl, p,
-                               hseed, training, pl.xd, pl.z, pl.nrm, pl.rowloss, HP<float>(d, GNN_SH_LOSS), st));
+  const bool ce = pl.loss_kind == GNN_LOSS_CE;
+  if (ce)
+    GNN_TRY(gnn_head_ce_fwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, ldl, p,
+                                hseed, training, pl.xd, pl.z, pl.nrm, pl.rowloss, HP<float>(d, GNN_SH_LOSS), pl.lse,
+                                st));
+  else
+    GNN_TRY(gnn_head_bce_fwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, ldl,
+                                 p, hseed, training, pl.xd, pl.z, pl.nrm, pl.rowloss, HP<float>(d, GNN_SH_LOSS), st));
   // ------------------------------------------------------------------ backward
-  GNN_TRY(gnn_head_bce_bwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, pl.C, labels, ldl, nullptr, p, hseed, training, pl.z,
-                               pl.nrm, pl.dz, pl.dXh, pl.Dh, st));
+  if (ce)
+    GNN_TRY(gnn_head_ce_bwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, pl.C, labels, ldl, nullptr, p, hseed, training, pl.z,
+                                pl.nrm, pl.dz, pl.dXh, pl.Dh, pl.lse, st));
+  else
+    GNN_TRY(gnn_head_bce_bwd_f32(top.Y, top.D, pl.Mh, pl.Dh, Wh, pl.C, labels, ldl, nullptr, p, hseed, training, pl.z,
+                                 pl.nrm, pl.dz, pl.dXh, pl.Dh, st));
   // gradient-ready events (GNN_SH_GRAD_EVENTS): the caller's DP exchange of a bucket starts there
   const int64_t* const E = HP<const int64_t>(d, GNN_SH_GRAD_EVENTS);
   auto grads_ready = [&](int64_t slot, hipStream_t s) -> int {
@@ -793,9 +809,9 @@ int gnn_eval_step_f32(const int64_t* d, float* logits, int64_t ldz, int32_t* cou
   GNN_TRY(r.open(d, (hipStream_t)stream));
   GNN_TRY(forward(r));  // training = 0, no timing records, phase 0
   const LayerBufs& top = pl.lb[pl.nl - 1];
-  return gnn_head_eval_f32(top.Y, top.D, pl.Mh, pl.Dh, HP<const float>(d, GNN_SH_HEAD_W),
-                           HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, d[GNN_SH_LDL], logits, ldz, pl.rowloss,
-                           pl.rowmask, loss, counts, mode, stream);
+  return gnn_head_eval_loss_f32(top.Y, top.D, pl.Mh, pl.Dh, HP<const float>(d, GNN_SH_HEAD_W),
+                                HP<const float>(d, GNN_SH_HEAD_B), pl.C, labels, d[GNN_SH_LDL], logits, ldz,
+                                pl.rowloss, pl.rowmask, loss, counts, mode, pl.loss_kind, stream);
 }
 
 }  // extern "C"

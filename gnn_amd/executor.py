@@ -25,7 +25,8 @@ from . import custom_sparse_ops as cso
 VERSION, MAX_LAYERS, HEADER, LAYER_SLOTS, SAGE, GCN = 1, 4, 24, 32, 0, 1
 (H_VERSION, H_LAYERS, H_KIND, H_X0, H_LDX0, H_F0, H_HEAD_W, H_HEAD_B, H_HEAD_GW, H_HEAD_GB, H_CLASSES, H_LABELS,
  H_LDL, H_HEAD_SEED, H_PDROP_BITS, H_TRAINING, H_LOSS, H_NHID, H_TIMING, H_GRAD_EVENTS, H_STAGE_EVENT,
- H_STAGE_LAYER, H_PHASE) = range(23)
+ H_STAGE_LAYER, H_PHASE, H_LOSS_KIND) = range(24)
+LOSS_BCE, LOSS_CE = 0, 1
 TIMING_SLOTS = 16
 (L_ROWPTR, L_COL, L_VAL, L_M, L_K, L_NNZ, L_TROWPTR, L_TCOL, L_TVAL, L_SAMPLED, L_NSAMPLED, L_RMAP, L_WW, L_BW,
  L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED) = range(25)
@@ -46,9 +47,11 @@ class NativeStep:
     returns the loss (a device scalar); the gradients are in the parameters' ``.grad``.
     ``evaluate(x0, adjs, sampled_nodes, labels)`` runs the forward alone through
     gnn_eval_step_f32 for validation / test batches (main.py:178-199, 217-241): loss, per-class
-    prediction counts and, on request, logits — the same parameters, no gradient touched."""
+    prediction counts and, on request, logits — the same parameters, no gradient touched.
+    ``sigmoid_loss`` picks the loss of both (GNN_SH_LOSS_KIND): BCE with logits, or softmax
+    cross-entropy over the float label rows (utils.loss with sigmoid_loss=False)."""
 
-    def __init__(self, model):
+    def __init__(self, model, sigmoid_loss: bool = True):
         from . import models
 
         enc = model.encoder
@@ -78,6 +81,7 @@ class NativeStep:
         d[H_VERSION] = VERSION
         d[H_LAYERS] = len(enc.gcs)
         d[H_KIND] = self.kind
+        d[H_LOSS_KIND] = LOSS_BCE if sigmoid_loss else LOSS_CE
         head = model.linear
         d[H_HEAD_W], d[H_HEAD_B] = _p(head.weight), _p(head.bias)
         d[H_HEAD_GW], d[H_HEAD_GB] = _p(g[id(head.weight)]), _p(g.get(id(head.bias)) if head.bias is not None else None)
@@ -229,14 +233,18 @@ class NativeStep:
             p.grad = gr
         return loss
 
-    def evaluate(self, x0, adjs, sampled_nodes, labels=None, mode: int = 0, want_logits: bool = False):
+    def evaluate(self, x0, adjs, sampled_nodes, labels=None, mode: int = 0, want_logits: bool = False,
+                 sigmoid_loss: Optional[bool] = None):
         """Forward only (gnn_eval_step_f32: no dropout whatever the model's mode, no backward, no
         gradient buffer touched) with the fused evaluation head. Returns (loss, counts, logits),
         device tensors, nothing synchronised: loss a scalar and counts int32 [3, C] = per-class
         (tp, fp, fn) of this batch (gnn_amd.metrics; mode 0 sigmoid, 1 argmax) — both None
-        without labels (predict, which always returns the logits); logits [M, C] or None."""
+        without labels (predict, which always returns the logits); logits [M, C] or None.
+        sigmoid_loss: the loss of this call (None: the executor's own); independent of mode."""
         want_logits = want_logits or labels is None
         d = self._desc(x0, adjs, sampled_nodes, labels, seeds=False, forward_only=True)
+        if sigmoid_loss is not None:
+            d[H_LOSS_KIND] = LOSS_BCE if sigmoid_loss else LOSS_CE
         dev = x0.device
         C = int(d[H_CLASSES])
         loss = counts = logits = None

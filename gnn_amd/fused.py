@@ -420,3 +420,69 @@ def head_bce_loss(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], l
     tr = bool(training and p > 0)
     seed = int(torch.randint(0, 2**62, (1,)).item()) if tr else 0
     return HeadBCEFn.apply(x, W, b, labels, float(p), tr, seed)
+
+
+class HeadCEFn(torch.autograd.Function):
+    """GNN's head with the softmax cross-entropy loss (models.py:90-97 + utils.py:138-140,
+    sigmoid_loss=False): CrossEntropyLoss("none")(linear(dropout(normalize(x))), float label rows),
+    weighted 1/M and summed, as HeadBCEFn: one HIP pass each way (gnn_head_ce_fwd_f32 /
+    gnn_head_ce_bwd_f32; the forward keeps each row's log-sum-exp for the backward), then
+    dW = dzᵀ·xd and db = Σ_rows dz. Returns (loss, logits)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, labels, p: float, training: bool, seed: int):
+        M, D = x.shape
+        C = W.shape[0]
+        dev = x.device
+        W = W.contiguous()
+        b = b.contiguous() if b is not None else None
+        labels = labels if (labels.dim() == 2 and labels.stride(1) == 1) else labels.contiguous()
+        if labels.dtype != torch.float32:
+            labels = labels.float()
+        xd = torch.empty((M, D), dtype=torch.float32, device=dev)
+        z = torch.empty((M, C), dtype=torch.float32, device=dev)
+        nrm = torch.empty(M, dtype=torch.float32, device=dev)
+        lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+        rowloss = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gnn_head_ce_fwd_f32(x.data_ptr(), x.stride(0), M, D, W.data_ptr(), _ptr(b), C,
+                                                  labels.data_ptr(), labels.stride(0), float(p), seed,
+                                                  int(training), xd.data_ptr(), z.data_ptr(), nrm.data_ptr(),
+                                                  rowloss.data_ptr(), loss.data_ptr(), lse.data_ptr(), _stream(dev)),
+                   "gnn_head_ce_fwd_f32")
+        ctx.save_for_backward(x, W, labels, xd, z, nrm, lse)
+        ctx.cfg = (float(p), int(training), int(seed), b is not None)
+        ctx.mark_non_differentiable(z)
+        ctx.set_materialize_grads(False)  # no zero-filled gradient for the logits output
+        return loss, z
+
+    @staticmethod
+    def backward(ctx, gloss, _gz):
+        x, W, labels, xd, z, nrm, lse = ctx.saved_tensors
+        p, training, seed, has_bias = ctx.cfg
+        M, D = x.shape
+        C = W.shape[0]
+        dev = x.device
+        gloss = gloss.contiguous()
+        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        dx = torch.empty((M, D), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gnn_head_ce_bwd_f32(x.data_ptr(), x.stride(0), M, D, W.data_ptr(), C,
+                                                  labels.data_ptr(), labels.stride(0), gloss.data_ptr(), p, seed,
+                                                  training, z.data_ptr(), nrm.data_ptr(), dz.data_ptr(),
+                                                  dx.data_ptr(), D, lse.data_ptr(), _stream(dev)),
+                   "gnn_head_ce_bwd_f32")
+        dW = torch.mm(dz.t(), xd) if ctx.needs_input_grad[1] else None
+        db = dz.sum(0) if (has_bias and ctx.needs_input_grad[2]) else None
+        return dx, dW, db, None, None, None, None
+
+
+def head_ce_loss(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], labels: torch.Tensor,
+                 p: float = 0.0, training: bool = False):
+    """(loss, logits) of GNN's head with the softmax cross-entropy loss — see HeadCEFn. Raises
+    when the operands are outside the kernel's contract (callers check head_supported first)."""
+    if not head_supported(x, W, labels):
+        raise RuntimeError("head_ce_loss: fp32 CUDA x (M x D, D % 4 == 0, D <= 2048, 16-byte rows), "
+                           "at most 256 classes, labels M x C")
+    tr = bool(training and p > 0)
+    seed = int(torch.randint(0, 2**62, (1,)).item()) if tr else 0
+    return HeadCEFn.apply(x, W, b, labels, float(p), tr, seed)

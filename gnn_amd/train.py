@@ -57,7 +57,7 @@ class Trainer:
 
             if ex.enabled():
                 try:
-                    self.executor = ex.NativeStep(model)
+                    self.executor = ex.NativeStep(model, sigmoid_loss=sigmoid_loss)
                 except ValueError:
                     self.executor = None
         self.world = 1
@@ -249,8 +249,7 @@ class Evaluator:
         self.native_batches = 0
 
     def _native(self, x0, adjs, sampled_nodes, labels) -> bool:
-        # the executor's loss is the BCE-with-logits one
-        return (self.executor is not None and (labels is None or self.sigmoid_loss)
+        return (self.executor is not None
                 and self.executor.supports(x0, adjs, sampled_nodes, labels, inference=True))
 
     def _eval_mode(self):
@@ -265,7 +264,8 @@ class Evaluator:
         from . import metrics
 
         if self._native(x0, adjs, sampled_nodes, labels):
-            loss, counts, _ = self.executor.evaluate(x0, adjs, sampled_nodes, labels, mode=self.mode)
+            loss, counts, _ = self.executor.evaluate(x0, adjs, sampled_nodes, labels, mode=self.mode,
+                                                     sigmoid_loss=self.sigmoid_loss)
             self.native_batches += 1
         else:
             was_training = self._eval_mode()

@@ -134,6 +134,23 @@ int gnn_head_bce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, cons
                          int training, const float* z, const float* norm, float* dz, float* dX, int64_t lddx,
                          void* stream);
 
+/* The same head with the softmax cross-entropy loss (utils.py:138-140, sigmoid_loss = False:
+ * CrossEntropyLoss(reduction "none") over float target rows, weighted 1/M and summed):
+ *   lse_r = m_r + log Σ_j exp(z_rj - m_r), m_r = max_j z_rj       -> stored lse[M] for the backward
+ *   *loss = Σ_rows Σ_j y_rj (lse_r - z_rj) / M   (subtracted per class; rows summed in fixed order)
+ * The row pass, the dropout hash and the seed are those of gnn_head_bce_fwd_f32: xd, z and norm
+ * are bit-identical to what it writes for the same inputs. The targets are probabilities, as in
+ * torch: a row need not sum to 1, and an all-zero row contributes 0. Same contract (D % 4 == 0,
+ * D <= 2048, C <= 256, 16-byte rows, labels M x C with row stride ldl). No atomics: deterministic.
+ * Backward: dz = (*grad_loss) (exp(z - lse) Σ_j y_j - y) / M, then dX as in the BCE backward. */
+int gnn_head_ce_fwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                        int64_t C, const float* labels, int64_t ldl, float p, uint64_t seed, int training, float* xd,
+                        float* z, float* norm, float* rowloss, float* loss, float* lse, void* stream);
+int gnn_head_ce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, int64_t C,
+                        const float* labels, int64_t ldl, const float* grad_loss, float p, uint64_t seed, int training,
+                        const float* z, const float* norm, float* dz, float* dX, int64_t lddx, const float* lse,
+                        void* stream);
+
 /* Evaluation head (head.hip): the forward above with training = 0 for a validation / test batch
  * (main.py:178-199, 217-241: model.eval(), forward, utils.loss, utils.calc_f1) — no dropout, no
  * xd / norm stores — plus the per-class prediction counts utils.calc_f1 (utils.py:142-149) feeds
@@ -159,6 +176,15 @@ int gnn_head_bce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, cons
 int gnn_head_eval_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
                       int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
                       uint64_t* rowmask, float* loss, int32_t* counts, int mode, void* stream);
+
+/* gnn_head_eval_f32 with the loss chosen by loss_kind: 0 = the BCE-with-logits terms (what
+ * gnn_head_eval_f32 computes: it forwards here with kind 0), 1 = the softmax cross-entropy terms of
+ * gnn_head_ce_fwd_f32, bit-identical to its loss with training = 0. Logits, masks and counts do
+ * not depend on the kind, and mode is independent of it. Any other kind returns a status before
+ * anything is launched. */
+int gnn_head_eval_loss_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const float* W, const float* bias,
+                           int64_t C, const float* labels, int64_t ldl, float* z, int64_t ldz, float* rowloss,
+                           uint64_t* rowmask, float* loss, int32_t* counts, int mode, int loss_kind, void* stream);
 
 #ifdef __cplusplus
 }

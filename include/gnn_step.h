@@ -5,7 +5,7 @@
  * sampled_nodes) -> utils.loss -> loss.backward(); models.py:6-97, utils.py:129-140) — the
  * ~45 autograd Functions / ctypes calls per step of gnn_amd.models' fused path — with ONE call
  * that issues the same kernels (aggregation gnn_spmm_csr_f32[_ex], row gather, split3 / rocBLAS
- * GEMMs, gnn_sage_norm_*, gnn_head_bce_*) with the same routing and dropout seeds. Gradients
+ * GEMMs, gnn_sage_norm_*, gnn_head_bce_* or gnn_head_ce_*) with the same routing and dropout seeds. Gradients
  * are written into caller-provided buffers; clip / all-reduce / Adam stay with the caller
  * (gnn_optim.h). Stream-ordered; every intermediate lives in one caller-provided workspace of
  * gnn_train_step_workspace_bytes(desc) bytes (256-byte aligned). Returns 0 or a status (text:
@@ -37,6 +37,11 @@
  *     step's gradient all-reduce runs: it reads only the batch, never a parameter); 2 = the step
  *     of a batch whose layer-0 aggregation a phase-1 call with the same descriptor already issued
  *     into the same workspace (it is not issued again). 0 and 1 + 2 give the same results.
+ *     and the loss kind (GNN_SH_LOSS_KIND): GNN_LOSS_BCE (0, so every descriptor built before the
+ *     slot had a meaning) = BCE with logits (utils.loss with sigmoid_loss), GNN_LOSS_CE = softmax
+ *     cross-entropy over the float label rows (sigmoid_loss = False); it picks the head's forward /
+ *     backward pair (gnn_layers.h) and nothing else. Any other value is refused: both
+ *     *_workspace_bytes functions return 0 and neither step function launches anything.
  *   layer l: the operand A (rowptr / col / val, M x K, nnz) and its transpose (K x M, layers >= 1),
  *     sampled (int64 [M], SAGE) and rmap (int32 [K], rmap[sampled[i]] = i, SAGE layers >= 1),
  *     weights W_W / W_B (N x F row-major), biases, scale / offset, their gradient buffers, the
@@ -59,13 +64,15 @@ extern "C" {
 #define GNN_STEP_SAGE 0
 #define GNN_STEP_GCN 1
 #define GNN_STEP_TIMING_SLOTS 16
+#define GNN_LOSS_BCE 0
+#define GNN_LOSS_CE 1
 
 enum {
   GNN_SH_VERSION = 0, GNN_SH_LAYERS = 1, GNN_SH_KIND = 2, GNN_SH_X0 = 3, GNN_SH_LDX0 = 4, GNN_SH_F0 = 5,
   GNN_SH_HEAD_W = 6, GNN_SH_HEAD_B = 7, GNN_SH_HEAD_GW = 8, GNN_SH_HEAD_GB = 9, GNN_SH_CLASSES = 10,
   GNN_SH_LABELS = 11, GNN_SH_LDL = 12, GNN_SH_HEAD_SEED = 13, GNN_SH_PDROP_BITS = 14, GNN_SH_TRAINING = 15,
   GNN_SH_LOSS = 16, GNN_SH_NHID = 17, GNN_SH_TIMING = 18, GNN_SH_GRAD_EVENTS = 19, GNN_SH_STAGE_EVENT = 20,
-  GNN_SH_STAGE_LAYER = 21, GNN_SH_PHASE = 22
+  GNN_SH_STAGE_LAYER = 21, GNN_SH_PHASE = 22, GNN_SH_LOSS_KIND = 23
 };
 enum {
   GNN_SL_ROWPTR = 0, GNN_SL_COL = 1, GNN_SL_VAL = 2, GNN_SL_M = 3, GNN_SL_K = 4, GNN_SL_NNZ = 5,
@@ -81,9 +88,9 @@ int gnn_train_step_f32(const int64_t* desc, void* workspace, size_t workspace_by
 /* Forward-only step for validation / test batches (main.py:178-199, 217-241: model.eval(), the
  * same staging and forward, utils.loss, utils.calc_f1): the training step's forward with
  * training = 0 — the same kernels with the same routing, issued by the same code — and then the
- * evaluation head (gnn_head_eval_f32, gnn_layers.h): the loss, the logits (M_top x C, row stride
+ * evaluation head (gnn_head_eval_loss_f32, gnn_layers.h): the loss (of GNN_SH_LOSS_KIND), the logits (M_top x C, row stride
  * ldz; NULL: not written) and the per-class prediction counts[3][C] (tp, fp, fn; int32,
- * overwritten; mode 0: sigmoid / multi-label, 1: argmax / single-label).
+ * overwritten; mode 0: sigmoid / multi-label, 1: argmax / single-label; independent of the loss kind).
  * Takes the same version-1 descriptor and reads only what a forward needs: gradient pointers,
  * transposes (GNN_SL_T*), GNN_SL_RMAP, the seeds, GNN_SH_TRAINING, GNN_SH_TIMING and
  * GNN_SH_GRAD_EVENTS are ignored and may be 0; GNN_SH_PHASE must be 0; GNN_SH_STAGE_EVENT is
