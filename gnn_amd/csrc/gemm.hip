@@ -151,6 +151,28 @@ __device__ __forceinline__ float frag(const float* __restrict__ S, int r, int k)
   else return S[r * Stage<BKT>::MM_LD + k];
 }
 
+// A wave's 2 x NB accumulator blocks (tile origin m0, n0; wave wm, wn) into Cb, row stride ldo,
+// edge-guarded: C, or with split k the split's slab.
+// C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
+template <int NB>
+__device__ __forceinline__ void store_acc(const f16v (&acc)[2][NB], float* Cb, int64_t ldo, int M, int N, int m0,
+                                          int n0, int wm, int wn, int li, int lh) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int n = n0 + wn * (32 * NB) + j * 32 + li;
+      if (n >= N) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        // the lane half is bit 2 of the row, clear in the other terms (m0 is a multiple of 128)
+        const int m = (m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2)) | (4 * lh);
+        if (m < M) Cb[(int64_t)m * ldo + n] = acc[i][j][r];
+      }
+    }
+  }
+}
+
 // C (or a split-k partial) = A · B over k in [kbeg, kend) for one 128 x 128 tile.
 template <bool AK, bool BKM, int VA, int VB, int BKT>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb,
@@ -217,30 +239,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(Batch bt, int M, int N, i
     }
     __syncthreads();
   }
-
-  // C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-  float* __restrict__ Cb;
-  int64_t ldo;
-  if (splits > 1) {
-    Cb = part + (int64_t)blockIdx.z * M * N;
-    ldo = N;
-  } else {
-    Cb = bt.C[b];
-    ldo = ldc;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-        if (m < M) Cb[(int64_t)m * ldo + n] = acc[i][j][r];
-      }
-    }
-  }
+  store_acc<2>(acc, splits > 1 ? part + (int64_t)blockIdx.z * M * N : bt.C[b], splits > 1 ? N : ldc, M, N, m0, n0, wm,
+               wn, li, lk);
 }
 
 // C[b] = sum over splits of the partial tiles, in split order; 4 consecutive outputs per thread
@@ -388,23 +388,21 @@ __device__ __forceinline__ int s3_voff(int64_t ld, int r0, int rlim, int t, cons
 // out half-major, [h][row]: a ds_write_b128 group of 8 lanes then covers 128 contiguous bytes
 // (the [row][h] image was 2-way: 0.33 of the LDS cycles of the weight-gradient kernels), and
 // each ds_read_b128 group {0-3,12-15,20-27} / {4-11,16-19,28-31} still covers 64 banks.
-template <bool KMAJ>
+// R: rows of the image (128, or the wide tile's 256 B rows).
+template <bool KMAJ, int R>
 __device__ __forceinline__ int s3_chunk(int row, int h) {
-  if constexpr (KMAJ) return (h * BM + row) * 8;
+  if constexpr (KMAJ) return (h * R + row) * 8;
   else return (2 * row + (h ^ ((row >> 3) & 1))) * 8;
 }
 
-// Split 8 floats into their three bf16 pieces and store them into the stage's images.
-template <bool KMAJ>
-__device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int t, const float v[8]) {
-  const int rr = KMAJ ? (t & 127) : (t >> 1);
-  const int kh = KMAJ ? (t >> 7) : (t & 1);
+// Split 8 floats into their three bf16 pieces (by truncation, x = h + m + l exactly), two
+// elements packed per word.
+__device__ __forceinline__ void split8(const float v[8], u4v& ph, u4v& pm, u4v& pl) {
   // per pair of elements: 4 v_and, 4 v_sub_f32 and 3 v_perm (one per piece, packing the two high
   // halves). The kernel is bound by the SIMD's issue port (VALU + MFMA issue); the subtractions
   // stay scalar: the packed form (v_pk_add_f32, two elements per instruction) measured 2-5 %
   // slower on every layer pair (profiles/round5/gemm_split/), the element-wise and/or form
   // (and + or_sdwa + lshr + and_or + moves, 214 VALU per two k tiles) slower still.
-  u4v ph, pm, pl;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float x0 = v[2 * j], x1 = v[2 * j + 1];
@@ -417,59 +415,106 @@ __device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int t, 
     pm[j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
     pl[j] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
   }
-  const int off = s3_chunk<KMAJ>(rr, kh);
+}
+
+// 8 floats of (image row rr, k half kh) split into the stage's three piece images, each R x 16 bf16.
+template <bool KMAJ, int R>
+__device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int rr, int kh, const float v[8]) {
+  u4v ph, pm, pl;
+  split8(v, ph, pm, pl);
+  const int off = s3_chunk<KMAJ, R>(rr, kh);
   *reinterpret_cast<u4v*>(S + off) = ph;
-  *reinterpret_cast<u4v*>(S + S3_PIECE + off) = pm;
-  *reinterpret_cast<u4v*>(S + 2 * S3_PIECE + off) = pl;
+  *reinterpret_cast<u4v*>(S + R * S3_BK + off) = pm;
+  *reinterpret_cast<u4v*>(S + 2 * R * S3_BK + off) = pl;
 }
 
-template <bool KMAJ>
+// The thread's own 8 floats of a 128-row operand tile (row and k half as s3_load deals them).
+template <bool KMAJ, int R>
+__device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int t, const float v[8]) {
+  s3_store<KMAJ, R>(S, KMAJ ? (t & 127) : (t >> 1), KMAJ ? (t >> 7) : (t & 1), v);
+}
+
+template <bool KMAJ, int R>
 __device__ __forceinline__ bf8v s3_frag(const unsigned short* __restrict__ S, int piece, int row, int h) {
-  return __builtin_bit_cast(bf8v, *reinterpret_cast<const u4v*>(S + piece * S3_PIECE + s3_chunk<KMAJ>(row, h)));
+  return __builtin_bit_cast(bf8v, *reinterpret_cast<const u4v*>(S + piece * R * S3_BK + s3_chunk<KMAJ, R>(row, h)));
 }
 
-// The six piece products of one k16 step into the wave's 2 x 2 accumulators (small terms first).
-template <bool AK, bool BKM>
+// The six piece products of one k16 step into the wave's 2 x NB accumulators (small terms first;
+// per B block its three pieces, then the six products: the same order per output at every NB).
+// The A image has 128 rows, the B image the tile's 64 NB.
+template <bool AK, bool BKM, int NB>
 __device__ __forceinline__ void s3_mma(const unsigned short* __restrict__ Sa, const unsigned short* __restrict__ Sb,
-                                       int ra0, int rb0, int li, int lh, f16v acc[2][2]) {
-  bf8v a[2][3], bb[2][3];
+                                       int ra0, int rb0, int li, int lh, f16v (&acc)[2][NB]) {
+  constexpr int G = NB == 2 ? 2 : 1;  // B blocks whose pieces are held at once (NB = 4 has no registers for two)
+  bf8v a[2][3], bb[G][3];
 #pragma unroll
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      a[i][p] = s3_frag<AK>(Sa, p, ra0 + i * 32 + li, lh);
-      bb[i][p] = s3_frag<BKM>(Sb, p, rb0 + i * 32 + li, lh);
+      a[i][p] = s3_frag<AK, BM>(Sa, p, ra0 + i * 32 + li, lh);
+      if constexpr (G == 2) bb[i][p] = s3_frag<BKM, 64 * NB>(Sb, p, rb0 + i * 32 + li, lh);
     }
-  constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-  constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
-  for (int q = 0; q < 6; ++q)
+  for (int j0 = 0; j0 < NB; j0 += G) {
+    if constexpr (G == 1) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+      for (int p = 0; p < 3; ++p) bb[0][p] = s3_frag<BKM, 64 * NB>(Sb, p, rb0 + j0 * 32 + li, lh);
+    }
+    constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
+    constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], bb[j][PB[q]], acc[i][j], 0, 0, 0);
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+          acc[i][j0 + g] =
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], bb[g][PB[q]], acc[i][j0 + g], 0, 0, 0);
+  }
 }
 
-// three workgroups per CU: LDS 48 KB each, registers capped at 168 (3 waves per SIMD)
-template <bool AK, bool BKM, int VA, int VB, bool IDX = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb,
-                                                         int64_t ldc, int splits, int klen, float* __restrict__ part,
-                                                         int64_t abytes, int64_t bbytes, int xcd_map,
-                                                         int tail_base = 0, int tail_s = 0) {
+// The XCD tile map: the tile (x, y, z) that workgroup (bx, by, bz) of a (gx, gy, gz) grid takes.
+// Consecutive tiles (the n tiles of one m row panel) go to one XCD (workgroups are dealt to the
+// 8 XCDs round-robin), so a row panel of A is fetched into one L2 instead of up to four.
+__device__ __forceinline__ int3 xcd_tile(int gx, int gy, unsigned gz, unsigned bx, unsigned by, unsigned bz) {
+  const int total = gx * gy * gz;
+  const int hw = bx + gx * (by + gy * bz);
+  const int per = total >> 3;
+  const int lg = hw < per * 8 ? (hw & 7) * per + (hw >> 3) : hw;
+  return make_int3(lg % gx, (lg / gx) % gy, lg / (gx * gy));
+}
+
+// NB: 32-column blocks per wave; the workgroup's tile is 128 x 64 NB.
+//  * NB = 2, the default: 128 x 128, three workgroups per CU: LDS 48 KB each, registers capped at
+//    168 (3 waves per SIMD).
+//  * NB = 4, "wide" (round 6; GNN_GEMM_WIDE, see use_wide): twice the output per wave.
+//    The 128 x 128 tile gives each wave a 64 x 64 output: per k16 stage 24 MFMAs against 12
+//    ds_read_b128, 16 split floats per thread and one barrier. At 128 x 256 (the same 2 x 2 waves,
+//    each 64 x 128 = 2 x 4 blocks of 32 x 32): per stage 48 MFMAs against 18 reads, 24 split floats
+//    per thread and still one barrier — a quarter fewer LDS reads and split instructions per MFMA
+//    and half the barriers. The price is the register file: 128 accumulators, so two workgroups
+//    per CU (8 waves, up to 256 registers) instead of three, and LDS 72 KB per workgroup.
+// The B operand of a stage is NB / 2 128-row halves, each loaded, split and stored the same way,
+// and every output element accumulates the same pieces in the same order at either width (per k16
+// step the six products h·h .. l·h, small terms first): whole tiles are bit-identical.
+// Tail-tile mode (tail_s > 0, see tail_plan) is NB = 2 only.
+template <bool AK, bool BKM, int VA, int VB, bool IDX, int NB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 2 ? 3 : 2, NB == 2 ? 3 : 2))) void
+gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int splits, int klen,
+               float* __restrict__ part, int64_t abytes, int64_t bbytes, int xcd_map, int tail_base = 0,
+               int tail_s = 0) {
+  constexpr int TN = 64 * NB;  // tile width = rows of the B images
+  constexpr int NH = NB / 2;   // 128-row halves of the B tile
   __shared__ __attribute__((aligned(16))) unsigned short As[2][S3_OPER];
-  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][S3_OPER];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * S3_OPER];
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wid = t >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  // Tile of this workgroup. xcd_map: consecutive tiles (the n tiles of one m row panel)
-  // go to one XCD (workgroups are dealt to the 8 XCDs round-robin), so a row panel of A is
-  // fetched into one L2 instead of up to four.
   int tx = blockIdx.x, ty = blockIdx.y, tz = blockIdx.z;
   int b, split;
   int piece = -1;  // tail mode: this workgroup's k piece of a tail tile (slot in the piece slab)
-  if (tail_s > 0) {
+  if (NB == 2 && tail_s > 0) {
     // 1-D grid: tiles [0, tail_base) whole (XCD map over them), then each tail tile as tail_s
     // k pieces (see tail_plan)
     const int gx = (N + BN - 1) / BN, gy = (M + BM - 1) / BM;
@@ -489,21 +534,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     b = lg / (gx * gy);
   } else {
     if (xcd_map) {
-      const int gx = gridDim.x, gy = gridDim.y;
-      const int total = gx * gy * gridDim.z;
-      const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-      const int per = total >> 3;
-      const int lg = hw < per * 8 ? (hw & 7) * per + (hw >> 3) : hw;
-      tx = lg % gx;
-      ty = (lg / gx) % gy;
-      tz = lg / (gx * gy);
+      const int3 tile = xcd_tile(gridDim.x, gridDim.y, gridDim.z, blockIdx.x, blockIdx.y, blockIdx.z);
+      tx = tile.x, ty = tile.y, tz = tile.z;
     }
     b = tz / splits;
     split = tz % splits;
   }
   const int m0 = ty * BM;
-  const int n0 = tx * BN;
-  const bool whole = tail_s > 0 && piece < 0;
+  const int n0 = tx * TN;
+  const bool whole = NB == 2 && tail_s > 0 && piece < 0;
   const int kbeg = whole ? 0 : split * klen;
   const int kend = whole ? K : min(K, kbeg + klen);
   const float* __restrict__ A = bt.A[b];
@@ -512,33 +551,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   // IDX instantiations: A indexed when m-major, B when k-major (the two GraphSAGE x[sampled] uses)
   const int64_t* __restrict__ ia = (IDX && !AK) ? bt.ia[b] : nullptr;
   const int64_t* __restrict__ ib = (IDX && BKM) ? bt.ib[b] : nullptr;
-  const int voa = s3_voff<AK>(lda, m0, M, t, ia), vob = s3_voff<BKM>(ldb, n0, N, t);
+  const int voa = s3_voff<AK>(lda, m0, M, t, ia);
+  const int vob0 = s3_voff<BKM>(ldb, n0, N, t);
+  const int vob1 = NH == 2 ? s3_voff<BKM>(ldb, n0 + BN, N, t) : 0;  // the wide tile's second B half
 
-  f16v acc[2][2];
+  // The wide form keeps each operand's (row, k half) of the thread in registers, as its stores
+  // take two B rows; re-deriving them in every store cost it 2-4 VGPRs of its 256.
+  const int ar = AK ? (t & 127) : (t >> 1), ah = AK ? (t >> 7) : (t & 1);     // A's (row, k half)
+  const int br = BKM ? (t & 127) : (t >> 1), bh = BKM ? (t >> 7) : (t & 1);  // B's, per 128-row half
+  f16v acc[2][NB];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f16v(0.0f);
+    for (int j = 0; j < NB; ++j) acc[i][j] = f16v(0.0f);
 
   // Two register sets: tile kt+2's loads are in flight while tile kt is multiplied and tile
   // kt+1 (loaded one tile earlier) is split into the other LDS stage.
-  float ra[2][8], rb[2][8];
+  float ra[2][8], rb[2][8 * NH];
   // The main loop runs over the full k tiles with branch-free loads: a prefetch past the last
   // full tile re-reads that tile (never multiplied). A divergent guarded load inside the loop
   // made the compiler join two register sets and wait for ALL loads (vmcnt(0)) before the
   // MFMAs, i.e. no prefetch at all. The k tail (K % 16) runs once after the loop.
   const int nfull = (kend - kbeg) / S3_BK;
-  auto load_ab = [&](int kt, float(&xa)[8], float(&xb)[8]) {
+  auto load_ab = [&](int kt, float(&xa)[8], float(&xb)[8 * NH]) {
     const int k0 = kbeg + min(kt, nfull - 1) * S3_BK;
     s3_load<AK, VA, false>(rsa, A, lda, voa, m0, M, k0, kend, t, xa);
     if (IDX && BKM && ib)
-      s3_load<BKM, VB, false, true>(rsb, B, ldb, vob, n0, N, k0, kend, t, xb, ib);
+      s3_load<BKM, VB, false, true>(rsb, B, ldb, vob0, n0, N, k0, kend, t, xb, ib);
     else
-      s3_load<BKM, VB, false>(rsb, B, ldb, vob, n0, N, k0, kend, t, xb);
+      s3_load<BKM, VB, false>(rsb, B, ldb, vob0, n0, N, k0, kend, t, xb);
+    if constexpr (NH == 2) {
+      if (IDX && BKM && ib)
+        s3_load<BKM, VB, false, true>(rsb, B, ldb, vob1, n0 + BN, N, k0, kend, t, xb + 8, ib);
+      else
+        s3_load<BKM, VB, false>(rsb, B, ldb, vob1, n0 + BN, N, k0, kend, t, xb + 8);
+    }
   };
-  auto store_ab = [&](int stage, const float(&xa)[8], const float(&xb)[8]) {
-    s3_store<AK>(As[stage], t, xa);
-    s3_store<BKM>(Bs[stage], t, xb);
+  auto store_ab = [&](int stage, const float(&xa)[8], const float(&xb)[8 * NH]) {
+    if constexpr (NH == 2) {
+      s3_store<AK, BM>(As[stage], ar, ah, xa);
+      s3_store<BKM, TN>(Bs[stage], br, bh, xb);
+      s3_store<BKM, TN>(Bs[stage], br + BN, bh, xb + 8);
+    } else {
+      s3_store<AK, BM>(As[stage], t, xa);
+      s3_store<BKM, TN>(Bs[stage], t, xb);
+    }
   };
   const int li = lane & 31, lh = lane >> 5;
   if (nfull > 0) {
@@ -550,17 +607,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (; kt + 1 < nfull; kt += 2) {
       // tile kt from stage 0; tile kt+1 (set 1) -> stage 1; set 0 <- tile kt+2
       load_ab(kt + 2, ra[0], rb[0]);
-      s3_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
       store_ab(1, ra[1], rb[1]);
       __syncthreads();
       // tile kt+1 from stage 1; tile kt+2 (set 0) -> stage 0; set 1 <- tile kt+3
       load_ab(kt + 3, ra[1], rb[1]);
-      s3_mma<AK, BKM>(As[1], Bs[1], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<AK, BKM, NB>(As[1], Bs[1], wm * 64, wn * (32 * NB), li, lh, acc);
       store_ab(0, ra[0], rb[0]);
       __syncthreads();
     }
     if (nfull & 1) {  // odd count: the last full tile is in stage 0
-      s3_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
       __syncthreads();
     }
   }
@@ -571,248 +628,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     else
       s3_load<AK, VA, true>(rsa, A, lda, voa, m0, M, k0, kend, t, ra[0]);
     if (IDX && BKM && ib)
-      s3_load<BKM, VB, true, true>(rsb, B, ldb, vob, n0, N, k0, kend, t, rb[0], ib);
+      s3_load<BKM, VB, true, true>(rsb, B, ldb, vob0, n0, N, k0, kend, t, rb[0], ib);
     else
-      s3_load<BKM, VB, true>(rsb, B, ldb, vob, n0, N, k0, kend, t, rb[0]);
+      s3_load<BKM, VB, true>(rsb, B, ldb, vob0, n0, N, k0, kend, t, rb[0]);
+    if constexpr (NH == 2) {
+      if (IDX && BKM && ib)
+        s3_load<BKM, VB, true, true>(rsb, B, ldb, vob1, n0 + BN, N, k0, kend, t, rb[0] + 8, ib);
+      else
+        s3_load<BKM, VB, true>(rsb, B, ldb, vob1, n0 + BN, N, k0, kend, t, rb[0] + 8);
+    }
     store_ab(0, ra[0], rb[0]);
     __syncthreads();
-    s3_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
+    s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
   }
 
-  if (piece >= 0) {  // a tail tile's k piece: the whole 128 x 128 tile, tile-local, into its slab slot
-    float* __restrict__ P = part + (int64_t)piece * (BM * BN);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          P[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * BN + wn * 64 + j * 32 + li] = acc[i][j][r];
-    return;
-  }
-  float* __restrict__ Cb;
-  int64_t ldo;
-  if (splits > 1) {
-    Cb = part + (int64_t)tz * M * N;
-    ldo = N;
-  } else {
-    Cb = bt.C[b];
-    ldo = ldc;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (m < M) Cb[(int64_t)m * ldo + n] = acc[i][j][r];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// "split3w": the split3 kernel with twice the output per wave (round 6).
-//
-// The 128 x 128 split3 tile gives each wave a 64 x 64 output: per k16 stage 24 MFMAs against 12
-// ds_read_b128, 16 split floats per thread and one barrier. Here the tile is 128 x 256 (the same
-// 2 x 2 waves, each 64 x 128 = 2 x 4 blocks of 32 x 32): per stage 48 MFMAs against 18 reads, 24
-// split floats per thread and still one barrier — a quarter fewer LDS reads and split
-// instructions per MFMA and half the barriers. The price is the register file: 128 accumulators,
-// so two workgroups per CU (8 waves) instead of three, and LDS 72 KB per workgroup. The B operand
-// of a stage is two 128-row halves, each loaded, split and stored exactly as split3 does its B.
-// Every output element accumulates the same pieces in the same order as split3 (per k16 step the
-// six products h·h .. l·h, small terms first): whole tiles are bit-identical to split3's.
-// ---------------------------------------------------------------------------------------------
-constexpr int W_BN = 2 * BN;  // 256
-
-// piece-image chunk offset (bf16 units) for an image of R rows (split3's s3_chunk at R = 128)
-template <bool KMAJ, int R>
-__device__ __forceinline__ int s3w_chunk(int row, int h) {
-  if constexpr (KMAJ) return (h * R + row) * 8;
-  else return (2 * row + (h ^ ((row >> 3) & 1))) * 8;
-}
-
-// split 8 floats of (row rr, k half kh) into the three piece images (each R x 16 bf16)
-template <bool KMAJ, int R>
-__device__ __forceinline__ void s3w_store(unsigned short* __restrict__ S, int rr, int kh, const float v[8]) {
-  u4v ph, pm, pl;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = v[2 * j], x1 = v[2 * j + 1];
-    const unsigned int h0 = __float_as_uint(x0) & 0xffff0000u, h1 = __float_as_uint(x1) & 0xffff0000u;
-    const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-    const unsigned int m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-    const float l0 = r0 - __uint_as_float(m0), l1 = r1 - __uint_as_float(m1);
-    ph[j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-    pm[j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-    pl[j] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
-  }
-  const int off = s3w_chunk<KMAJ, R>(rr, kh);
-  *reinterpret_cast<u4v*>(S + off) = ph;
-  *reinterpret_cast<u4v*>(S + R * S3_BK + off) = pm;
-  *reinterpret_cast<u4v*>(S + 2 * R * S3_BK + off) = pl;
-}
-
-template <bool KMAJ, int R>
-__device__ __forceinline__ bf8v s3w_frag(const unsigned short* __restrict__ S, int piece, int row, int h) {
-  return __builtin_bit_cast(bf8v, *reinterpret_cast<const u4v*>(S + piece * R * S3_BK + s3w_chunk<KMAJ, R>(row, h)));
-}
-
-// one k16 step: the wave's 2 x 4 blocks, per B block its three pieces, the six products in
-// split3's order
-template <bool AK, bool BKM>
-__device__ __forceinline__ void s3w_mma(const unsigned short* __restrict__ Sa, const unsigned short* __restrict__ Sb,
-                                        int ra0, int rb0, int li, int lh, f16v acc[2][4]) {
-  bf8v a[2][3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) a[i][p] = s3w_frag<AK, BM>(Sa, p, ra0 + i * 32 + li, lh);
-  constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-  constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    bf8v bb[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) bb[p] = s3w_frag<BKM, W_BN>(Sb, p, rb0 + j * 32 + li, lh);
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
+  if constexpr (NB == 2) {
+    if (piece >= 0) {  // a tail tile's k piece: the whole 128 x 128 tile, tile-local, into its slab slot
+      float* __restrict__ P = part + (int64_t)piece * (BM * BN);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], bb[PB[q]], acc[i][j], 0, 0, 0);
-  }
-}
-
-// two workgroups per CU: LDS 72 KB each, up to 256 registers (2 waves per SIMD)
-template <bool AK, bool BKM, int VA, int VB, bool IDX = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_s3w_kernel(
-    Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int splits, int klen, float* __restrict__ part,
-    int64_t abytes, int64_t bbytes, int xcd_map) {
-  __shared__ __attribute__((aligned(16))) unsigned short As[2][S3_OPER];
-  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][2 * S3_OPER];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wid = t >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-  int tx = blockIdx.x, ty = blockIdx.y, tz = blockIdx.z;
-  if (xcd_map) {  // consecutive tiles on one XCD (split3's map)
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int per = total >> 3;
-    const int lg = hw < per * 8 ? (hw & 7) * per + (hw >> 3) : hw;
-    tx = lg % gx;
-    ty = (lg / gx) % gy;
-    tz = lg / (gx * gy);
-  }
-  const int b = tz / splits;
-  const int split = tz % splits;
-  const int m0 = ty * BM;
-  const int n0 = tx * W_BN;
-  const int kbeg = split * klen;
-  const int kend = min(K, kbeg + klen);
-  const float* __restrict__ A = bt.A[b];
-  const float* __restrict__ B = bt.B[b];
-  const __amdgpu_buffer_rsrc_t rsa = s3_rsrc(A, abytes), rsb = s3_rsrc(B, bbytes);
-  const int64_t* __restrict__ ia = (IDX && !AK) ? bt.ia[b] : nullptr;
-  const int64_t* __restrict__ ib = (IDX && BKM) ? bt.ib[b] : nullptr;
-  const int voa = s3_voff<AK>(lda, m0, M, t, ia);
-  const int vob0 = s3_voff<BKM>(ldb, n0, N, t), vob1 = s3_voff<BKM>(ldb, n0 + BN, N, t);
-  const int ar = AK ? (t & 127) : (t >> 1), ah = AK ? (t >> 7) : (t & 1);     // A's (row, k half)
-  const int br = BKM ? (t & 127) : (t >> 1), bh = BKM ? (t >> 7) : (t & 1);  // B's, per 128-row half
-
-  f16v acc[2][4];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f16v(0.0f);
-
-  float ra[2][8], rb[2][16];
-  const int nfull = (kend - kbeg) / S3_BK;
-  auto load_b = [&](int k0, int half, int vob, float* xb, bool guard) {
-    if (guard) {
-      if (IDX && BKM && ib)
-        s3_load<BKM, VB, true, true>(rsb, B, ldb, vob, n0 + half * BN, N, k0, kend, t, xb, ib);
-      else
-        s3_load<BKM, VB, true>(rsb, B, ldb, vob, n0 + half * BN, N, k0, kend, t, xb);
-    } else {
-      if (IDX && BKM && ib)
-        s3_load<BKM, VB, false, true>(rsb, B, ldb, vob, n0 + half * BN, N, k0, kend, t, xb, ib);
-      else
-        s3_load<BKM, VB, false>(rsb, B, ldb, vob, n0 + half * BN, N, k0, kend, t, xb);
-    }
-  };
-  auto load_ab = [&](int kt, float(&xa)[8], float(&xb)[16]) {
-    const int k0 = kbeg + min(kt, nfull - 1) * S3_BK;
-    s3_load<AK, VA, false>(rsa, A, lda, voa, m0, M, k0, kend, t, xa);
-    load_b(k0, 0, vob0, xb, false);
-    load_b(k0, 1, vob1, xb + 8, false);
-  };
-  auto store_ab = [&](int stage, const float(&xa)[8], const float(&xb)[16]) {
-    s3w_store<AK, BM>(As[stage], ar, ah, xa);
-    s3w_store<BKM, W_BN>(Bs[stage], br, bh, xb);
-    s3w_store<BKM, W_BN>(Bs[stage], br + BN, bh, xb + 8);
-  };
-  const int li = lane & 31, lh = lane >> 5;
-  if (nfull > 0) {
-    load_ab(0, ra[0], rb[0]);
-    load_ab(1, ra[1], rb[1]);
-    store_ab(0, ra[0], rb[0]);
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 1 < nfull; kt += 2) {
-      load_ab(kt + 2, ra[0], rb[0]);
-      s3w_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 128, li, lh, acc);
-      store_ab(1, ra[1], rb[1]);
-      __syncthreads();
-      load_ab(kt + 3, ra[1], rb[1]);
-      s3w_mma<AK, BKM>(As[1], Bs[1], wm * 64, wn * 128, li, lh, acc);
-      store_ab(0, ra[0], rb[0]);
-      __syncthreads();
-    }
-    if (nfull & 1) {
-      s3w_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 128, li, lh, acc);
-      __syncthreads();
+          for (int r = 0; r < 16; ++r)
+            P[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * BN + wn * 64 + j * 32 + li] = acc[i][j][r];
+      return;
     }
   }
-  if (kbeg + nfull * S3_BK < kend) {  // k tail
-    const int k0 = kbeg + nfull * S3_BK;
-    if (IDX && !AK && ia)
-      s3_load<AK, VA, true, true>(rsa, A, lda, voa, m0, M, k0, kend, t, ra[0], ia);
-    else
-      s3_load<AK, VA, true>(rsa, A, lda, voa, m0, M, k0, kend, t, ra[0]);
-    load_b(k0, 0, vob0, rb[0], true);
-    load_b(k0, 1, vob1, rb[0] + 8, true);
-    store_ab(0, ra[0], rb[0]);
-    __syncthreads();
-    s3w_mma<AK, BKM>(As[0], Bs[0], wm * 64, wn * 128, li, lh, acc);
-  }
-  float* __restrict__ Cb;
-  int64_t ldo;
-  if (splits > 1) {
-    Cb = part + (int64_t)tz * M * N;
-    ldo = N;
-  } else {
-    Cb = bt.C[b];
-    ldo = ldc;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 128 + j * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (m < M) Cb[(int64_t)m * ldo + n] = acc[i][j][r];
-      }
-    }
-  }
+  store_acc<NB>(acc, splits > 1 ? part + (int64_t)tz * M * N : bt.C[b], splits > 1 ? N : ldc, M, N, m0, n0, wm, wn, li,
+                lh);
 }
 
 // ---------------------------------------------------------------------------------
@@ -850,20 +694,6 @@ __global__ __launch_bounds__(256) void gemm_tail_reduce_kernel(Batch bt, const f
 // order): results bit-identical to gnn_gemm_f32_split3 on shapes without split3's tail tiles
 // (tail_plan; with GNN_GEMM_TAIL=0 on every shape).
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void split_piece8(const float v[8], u4v& ph, u4v& pm, u4v& pl) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f2 x = f2{v[2 * j], v[2 * j + 1]};
-    const unsigned int h0 = __float_as_uint(x.x) & 0xffff0000u, h1 = __float_as_uint(x.y) & 0xffff0000u;
-    const f2 r = x - f2{__uint_as_float(h0), __uint_as_float(h1)};
-    const unsigned int m0 = __float_as_uint(r.x) & 0xffff0000u, m1 = __float_as_uint(r.y) & 0xffff0000u;
-    const f2 l = r - f2{__uint_as_float(m0), __uint_as_float(m1)};
-    ph[j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-    pm[j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-    pl[j] = __builtin_amdgcn_perm(__float_as_uint(l.y), __float_as_uint(l.x), 0x07060302u);
-  }
-}
-
 // One (128-row block, k tile) per workgroup. m-major source (element (r, k) = src[row(r)*ld + k]):
 // thread t takes row t >> 1, k half t & 1; k-major source (element (r, k) = src[row(k)*ld + r]):
 // row t & 127, the wave-uniform k half t >> 7 (each of the 8 loads is one coalesced k row).
@@ -891,7 +721,7 @@ __global__ __launch_bounds__(256) void p3_pack_kernel(const float* __restrict__ 
     }
   }
   u4v ph, pm, pl;
-  split_piece8(v, ph, pm, pl);
+  split8(v, ph, pm, pl);
   const int64_t plane = (int64_t)KT * Rp * 16;
   const int64_t o = ((int64_t)kt * Rp + r) * 16 + kh * 8;
   *reinterpret_cast<u4v*>(out + o) = ph;
@@ -918,14 +748,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const int wm = wid >> 1, wn = wid & 1;
   int tx = blockIdx.x, ty = blockIdx.y, tz = blockIdx.z;
   if (xcd_map) {
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int per = total >> 3;
-    const int lg = hw < per * 8 ? (hw & 7) * per + (hw >> 3) : hw;
-    tx = lg % gx;
-    ty = (lg / gx) % gy;
-    tz = lg / (gx * gy);
+    const int3 tile = xcd_tile(gridDim.x, gridDim.y, gridDim.z, blockIdx.x, blockIdx.y, blockIdx.z);
+    tx = tile.x, ty = tile.y, tz = tile.z;
   }
   const int b = tz / splits;
   const int split = tz % splits;
@@ -940,7 +764,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                                       (int)(3 * bplane * 2), 0x00020000);
   const int rr = t >> 1, kh = t & 1;
   const int voa = ((m0 + rr) * 16 + kh * 8) * 2, vob = ((n0 + rr) * 16 + kh * 8) * 2;  // bytes
-  const int off = s3_chunk<false>(rr, kh);
+  const int off = s3_chunk<false, BM>(rr, kh);
 
   f16v acc[2][2];
 #pragma unroll
@@ -968,6 +792,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     }
   };
   const int li = lane & 31, lh = lane >> 5;
+  // gemm_s3_kernel's k loop, copied (every k tile is whole here): a change to that pipeline has to
+  // be mirrored here. Shared through callables, it changed gemm_s3_kernel's own instructions.
   if (nfull > 0) {
     load_ab(0, ra[0], rb[0]);
     load_ab(1, ra[1], rb[1]);
@@ -976,41 +802,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     int kt = 0;
     for (; kt + 1 < nfull; kt += 2) {
       load_ab(kt + 2, ra[0], rb[0]);
-      s3_mma<false, false>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<false, false, 2>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
       store_ab(1, ra[1], rb[1]);
       __syncthreads();
       load_ab(kt + 3, ra[1], rb[1]);
-      s3_mma<false, false>(As[1], Bs[1], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<false, false, 2>(As[1], Bs[1], wm * 64, wn * 64, li, lh, acc);
       store_ab(0, ra[0], rb[0]);
       __syncthreads();
     }
     if (nfull & 1) {
-      s3_mma<false, false>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
+      s3_mma<false, false, 2>(As[0], Bs[0], wm * 64, wn * 64, li, lh, acc);
       __syncthreads();
     }
   }
-  float* __restrict__ Cb;
-  int64_t ldo;
-  if (splits > 1) {
-    Cb = part + (int64_t)tz * M * N;
-    ldo = N;
-  } else {
-    Cb = bt.C[b];
-    ldo = ldc;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (m < M) Cb[(int64_t)m * ldo + n] = acc[i][j][r];
-      }
-    }
-  }
+  store_acc<2>(acc, splits > 1 ? part + (int64_t)tz * M * N : bt.C[b], splits > 1 ? N : ldc, M, N, m0, n0, wm, wn, li, lh);
 }
 
 // Workgroup slots of the chip at each kernel's occupancy: f32-input kernel 2 per CU (80 KB of
@@ -1022,16 +827,17 @@ constexpr int64_t SLOTS_S3 = 3 * 256;
 // until the tiles x splits fill the slots once — never past them: a second, nearly empty
 // round of workgroups costs almost a full round (measured: 40 tiles x 12 splits = 480
 // workgroups 190 µs, x 13 = 520 workgroups 255 µs). Each split keeps >= 256 of k.
-int pick_splits(int64_t M, int64_t N, int64_t K, int nbatch, int64_t slots) {
+// tile_n, slots: the kernel's tile width and its workgroup slots.
+int pick_splits(int64_t M, int64_t N, int64_t K, int nbatch, int64_t tile_n, int64_t slots) {
   if (const char* e = getenv("GNN_GEMM_SPLITS")) return std::max(1, atoi(e));  // experiments
-  const int64_t tiles = ceil_div(M, (int64_t)BM) * ceil_div(N, (int64_t)BN) * nbatch;
+  const int64_t tiles = ceil_div(M, (int64_t)BM) * ceil_div(N, tile_n) * nbatch;
   if (tiles * 2 > slots) return 1;
   int64_t s = slots / tiles;
   s = std::min<int64_t>(s, std::max<int64_t>(1, K / 256));
   return (int)std::max<int64_t>(1, std::min<int64_t>(s, 64));
 }
 
-// The wide split3 kernel (128 x 256 tiles, two workgroups per CU). Measured per layer pair against
+// The wide split3 kernel (NB = 4: 128 x 256 tiles, two workgroups per CU). Measured per layer pair against
 // split3 (scripts/gemm_bench.py, profiles/round6/gemm_wide/): the same rate per CU, so it wins only
 // where its tile count fills the chip's 512 slots once while split3's 128 x 128 tiles need a second,
 // partial round — the layer-0 forward (496 wide tiles against 992 on 768 slots: 118.8 vs 130.7 µs);
@@ -1043,6 +849,7 @@ int pick_splits(int64_t M, int64_t N, int64_t K, int nbatch, int64_t slots) {
 // and its tiles fill 85-100 % of the slots; 1: every product with N >= 256; 0 (default): never. A pure function of the shape and the batch count the split choice is made
 // for, so a product launched alone (gemm_split3_as_batch) takes the same kernel and k splits as inside
 // its batch, and the workspace query agrees with the launch.
+constexpr int W_BN = 2 * BN;  // 256
 constexpr int64_t SLOTS_S3W = 2 * 256;
 
 bool use_wide(int64_t M, int64_t N, int64_t K, int nbatch) {
@@ -1053,15 +860,6 @@ bool use_wide(int64_t M, int64_t N, int64_t K, int nbatch) {
   if (getenv("GNN_GEMM_SPLITS")) return false;  // split experiments keep split3
   const int64_t tw = ceil_div(M, (int64_t)BM) * ceil_div(N, (int64_t)W_BN) * nbatch;
   return tw * 100 >= SLOTS_S3W * 85 && tw <= SLOTS_S3W;
-}
-
-int pick_splits_wide(int64_t M, int64_t N, int64_t K, int nbatch) {
-  if (const char* e = getenv("GNN_GEMM_SPLITS")) return std::max(1, atoi(e));
-  const int64_t tiles = ceil_div(M, (int64_t)BM) * ceil_div(N, (int64_t)W_BN) * nbatch;
-  if (tiles * 2 > SLOTS_S3W) return 1;
-  int64_t s = SLOTS_S3W / tiles;
-  s = std::min<int64_t>(s, std::max<int64_t>(1, K / 256));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(s, 64));
 }
 
 // Tail tiles (split3, unsplit k): a launch of T tiles over 256 CUs whose last partial round holds
@@ -1100,11 +898,119 @@ bool tail_enabled() {
 size_t tail_bytes(const TailPlan& tp) { return (size_t)tp.rem * tp.s * BM * BN * sizeof(float); }
 
 enum Algo { ALGO_F32 = 0, ALGO_S3 = 1 };
+enum Kern { KERN_F32, KERN_S3, KERN_S3W };  // gemm_f32_kernel, gemm_s3_kernel at NB = 2, at NB = 4 (wide)
 
-int64_t slots_of(int algo) { return algo == ALGO_S3 ? SLOTS_S3 : SLOTS_F32; }
+// XCD-aware tile map for split3 (2-8 % per layer pair, scripts/gemm_bench.py); GNN_GEMM_XCD=0 turns it off
+bool xcd_map_enabled() {
+  const char* e = getenv("GNN_GEMM_XCD");
+  return !e || atoi(e) != 0;
+}
 
-// split_nbatch: the batch count the split-k choice is made for (0: nbatch). A product launched
-// alone with split_nbatch = n sums in exactly the order it would inside a batch of n.
+// What a product runs as: the kernel, the k splits and the tail plan (whatever GNN_GEMM_TAIL says:
+// the launch drops the plan when tails are off). The workspace query and the launch both ask here.
+// split_nbatch: the batch count the choice is made for (0: nbatch). A product launched alone with
+// split_nbatch = n sums in exactly the order it would inside a batch of n.
+// batch_index (with split_nbatch > 0): which product of the mimicked batch this launch is, so that
+// its tiles that the batched launch would run as tail pieces (tail_plan over the whole batch) run
+// as the same pieces here — the same sums, bit for bit.
+struct Plan {
+  Kern kern = KERN_F32;
+  int splits = 1;
+  TailPlan tp;
+  size_t bytes(int64_t M, int64_t N, int nbatch) const {
+    return splits > 1 ? (size_t)splits * nbatch * M * N * sizeof(float) : tail_bytes(tp);
+  }
+};
+
+Plan plan_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch, int split_nbatch = 0, int batch_index = -1) {
+  const int nb = split_nbatch > 0 ? split_nbatch : nbatch;
+  Plan p;
+  p.kern = algo != ALGO_S3 ? KERN_F32 : use_wide(M, N, K, nb) ? KERN_S3W : KERN_S3;
+  if (K > 0)
+    p.splits = p.kern == KERN_S3W   ? pick_splits(M, N, K, nb, W_BN, SLOTS_S3W)
+               : p.kern == KERN_S3 ? pick_splits(M, N, K, nb, BN, SLOTS_S3)
+                                   : pick_splits(M, N, K, nb, BN, SLOTS_F32);
+  if (p.kern != KERN_S3 || p.splits > 1 || K <= 0) return p;
+  if (split_nbatch == 0) {
+    p.tp = tail_plan(M, N, K, nbatch);
+  } else if (nbatch == 1 && batch_index >= 0) {
+    // one product of a batch of split_nbatch, launched alone: the batch's tail tiles that are this
+    // product's tiles [batch_index * T1, (batch_index + 1) * T1) run as the same k pieces
+    const TailPlan full = tail_plan(M, N, K, split_nbatch);
+    const int64_t T1 = ceil_div(M, (int64_t)BM) * ceil_div(N, (int64_t)BN);
+    const int64_t lo = (int64_t)batch_index * T1;
+    if (full.s > 0 && full.base < lo + T1) {
+      p.tp.base = (int)std::max<int64_t>(0, full.base - lo);
+      p.tp.s = full.s;
+      p.tp.rem = (int)(T1 - p.tp.base);
+    }
+  }
+  return p;
+}
+
+size_t workspace_bytes_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch) {
+  if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return 0;
+  return plan_of(algo, M, N, K, nbatch).bytes(M, N, nbatch);
+}
+
+// C[b] = the split-k slabs summed in split order (bt: C only).
+int launch_splitk_reduce(const Batch& bt, const float* part, int64_t M, int64_t N, int64_t ldc, int splits, int nbatch,
+                         hipStream_t st) {
+  const int64_t total = M * N * nbatch;
+  bool vec4 = ldc == N && (M * N) % 4 == 0;
+  for (int b = 0; b < nbatch; ++b) vec4 = vec4 && (uintptr_t)bt.C[b] % 16 == 0;
+  if (vec4) {
+    const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total / 4, (int64_t)256), 2048);
+    gemm_splitk_reduce4_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, M * N, splits, nbatch);
+    GNN_LAUNCHED("gemm_splitk_reduce4_kernel");
+  } else {
+    const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total, (int64_t)256), 2048);
+    gemm_splitk_reduce_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, (int)M, (int)N, ldc, splits, nbatch);
+    GNN_LAUNCHED("gemm_splitk_reduce_kernel");
+  }
+  return 0;
+}
+
+// Everything a GEMM kernel launch takes, and which kernel.
+struct Launch {
+  Kern kern;
+  bool idx;  // split3: some operand carries a row index
+  int bkt;   // f32 kernel: k depth of a stage
+  dim3 grid;
+  hipStream_t st;
+  Batch bt;
+  int M, N, K;
+  int64_t lda, ldb, ldc;
+  int splits, klen;
+  float* part;
+  int64_t abytes, bbytes;
+  int xcdm, tail_base, tail_s;
+};
+
+template <bool AK, bool BKM, int VA, int VB>
+void launch_gemm(const Launch& l) {
+  if (l.kern == KERN_F32) {
+    auto k = l.bkt == 16 ? gemm_f32_kernel<AK, BKM, VA, VB, 16> : gemm_f32_kernel<AK, BKM, VA, VB, 32>;
+    k<<<l.grid, dim3(256), 0, l.st>>>(l.bt, l.M, l.N, l.K, l.lda, l.ldb, l.ldc, l.splits, l.klen, l.part);
+    return;
+  }
+  const bool wide = l.kern == KERN_S3W;
+  auto k = wide ? gemm_s3_kernel<AK, BKM, VA, VB, false, 4> : gemm_s3_kernel<AK, BKM, VA, VB, false, 2>;
+  // row indices need an m-major A or a k-major B (gemm_run refuses the rest): no IDX form of <true, false>
+  if constexpr (!AK || BKM)
+    if (l.idx) k = wide ? gemm_s3_kernel<AK, BKM, VA, VB, true, 4> : gemm_s3_kernel<AK, BKM, VA, VB, true, 2>;
+  k<<<l.grid, dim3(256), 0, l.st>>>(l.bt, l.M, l.N, l.K, l.lda, l.ldb, l.ldc, l.splits, l.klen, l.part, l.abytes,
+                                    l.bbytes, l.xcdm, l.tail_base, l.tail_s);
+}
+
+template <bool AK, bool BKM>
+void launch_gemm(int va, int vb, const Launch& l) {
+  if (va == 4 && vb == 4) launch_gemm<AK, BKM, 4, 4>(l);
+  else if (va == 4) launch_gemm<AK, BKM, 4, 2>(l);
+  else if (vb == 4) launch_gemm<AK, BKM, 2, 4>(l);
+  else launch_gemm<AK, BKM, 2, 2>(l);
+}
+
 // Indexed operands (split3): ia / ib (per batch entry, NULL entries allowed) with the source's row
 // count a_rows / b_rows (its extent for the buffer range); A is indexable when m-major, B when
 // k-major.
@@ -1115,9 +1021,7 @@ struct RowIndex {
   int64_t b_rows = 0;
 };
 
-// batch_index (with split_nbatch > 0): which product of the mimicked batch this launch is, so that
-// its tiles that the batched launch would run as tail pieces (tail_plan over the whole batch) run
-// as the same pieces here — the same sums, bit for bit.
+// split_nbatch, batch_index: see plan_of.
 int gemm_run(int algo, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch, const float* const* A,
              int64_t lda, const float* const* B, int64_t ldb, float* const* C, int64_t ldc, void* workspace,
              size_t workspace_bytes, void* stream, int split_nbatch = 0, const RowIndex* ri = nullptr,
@@ -1130,7 +1034,8 @@ int gemm_run(int algo, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t
   GNN_REQUIRE(ldc >= N, "gnn_gemm_f32: ldc < N");
   GNN_REQUIRE(lda >= (a_kmajor ? M : K) && ldb >= (b_kmajor ? N : K), "gnn_gemm_f32: lda/ldb too small");
   GNN_REQUIRE(lda % 2 == 0 && ldb % 2 == 0, "gnn_gemm_f32: lda and ldb must be even (8-byte rows)");
-  Batch bt{};
+  Launch l{};
+  Batch& bt = l.bt;
   int va = 4, vb = 4;  // 16-byte loads where every row allows them, else 8-byte
   for (int b = 0; b < nbatch; ++b) {
     GNN_REQUIRE(C[b] && (K == 0 || (A[b] && B[b])), "gnn_gemm_f32: NULL operand %d", b);
@@ -1143,169 +1048,57 @@ int gemm_run(int algo, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t
     bt.ia[b] = ri && ri->ia ? ri->ia[b] : nullptr;
     bt.ib[b] = ri && ri->ib ? ri->ib[b] : nullptr;
   }
-  bool idx = false;
-  for (int b = 0; b < nbatch; ++b) idx = idx || bt.ia[b] || bt.ib[b];
-  GNN_REQUIRE(!idx || (algo == ALGO_S3 && (!ri->ia || !a_kmajor) && (!ri->ib || b_kmajor)),
+  for (int b = 0; b < nbatch; ++b) l.idx = l.idx || bt.ia[b] || bt.ib[b];
+  GNN_REQUIRE(!l.idx || (algo == ALGO_S3 && (!ri->ia || !a_kmajor) && (!ri->ib || b_kmajor)),
               "gnn_gemm: row indices need split3, an m-major A or a k-major B");
   // split3 addresses operands by 32-bit buffer offsets: operands of >= 2 GiB take the f32-input kernel
   const int64_t arows = (ri && ri->ia) ? ri->a_rows : (a_kmajor ? K : M);
   const int64_t brows = (ri && ri->ib) ? ri->b_rows : (b_kmajor ? K : N);
-  const int64_t abytes = K == 0 ? 0 : (arows - 1) * lda * 4 + (a_kmajor ? M : K) * 4;
-  const int64_t bbytes = K == 0 ? 0 : (brows - 1) * ldb * 4 + (b_kmajor ? N : K) * 4;
-  if (algo == ALGO_S3 && (abytes >= INT_MAX || bbytes >= INT_MAX)) {
-    GNN_REQUIRE(!idx, "gnn_gemm: indexed operand of >= 2 GiB");
+  l.abytes = K == 0 ? 0 : (arows - 1) * lda * 4 + (a_kmajor ? M : K) * 4;
+  l.bbytes = K == 0 ? 0 : (brows - 1) * ldb * 4 + (b_kmajor ? N : K) * 4;
+  if (algo == ALGO_S3 && (l.abytes >= INT_MAX || l.bbytes >= INT_MAX)) {
+    GNN_REQUIRE(!l.idx, "gnn_gemm: indexed operand of >= 2 GiB");
     algo = ALGO_F32;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (algo == ALGO_S3 && K > 0 && use_wide(M, N, K, split_nbatch > 0 ? split_nbatch : nbatch)) {
-    const int splits = pick_splits_wide(M, N, K, split_nbatch > 0 ? split_nbatch : nbatch);
-    int xcdm = 1;
-    if (const char* e = getenv("GNN_GEMM_XCD")) xcdm = atoi(e) != 0;
-    const int klen = splits > 1 ? (int)(ceil_div(ceil_div(K, (int64_t)splits), (int64_t)S3_BK) * S3_BK) : (int)K;
-    if (splits > 1) {
-      const size_t need = (size_t)splits * nbatch * M * N * sizeof(float);
-      GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_gemm_f32: workspace too small (%zu < %zu)",
-                  workspace_bytes, need);
-    }
-    const dim3 grid((unsigned)ceil_div(N, (int64_t)W_BN), (unsigned)ceil_div(M, (int64_t)BM),
-                    (unsigned)(nbatch * splits));
-    float* part = (float*)workspace;
-#define GNN_GEMMW_LAUNCH(AK, BK, VA, VB)                                                                        \
-  do {                                                                                                          \
-    if (idx)                                                                                                    \
-      gemm_s3w_kernel<AK, BK, VA, VB, true><<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb,   \
-                                                                        ldc, splits, klen, part, abytes, bbytes, \
-                                                                        xcdm);                                   \
-    else                                                                                                        \
-      gemm_s3w_kernel<AK, BK, VA, VB><<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb, ldc,    \
-                                                                  splits, klen, part, abytes, bbytes, xcdm);    \
-  } while (0)
-#define GNN_GEMMW_V(AK, BK)                                    \
-  do {                                                         \
-    if (va == 4 && vb == 4) GNN_GEMMW_LAUNCH(AK, BK, 4, 4);    \
-    else if (va == 4) GNN_GEMMW_LAUNCH(AK, BK, 4, 2);          \
-    else if (vb == 4) GNN_GEMMW_LAUNCH(AK, BK, 2, 4);          \
-    else GNN_GEMMW_LAUNCH(AK, BK, 2, 2);                       \
-  } while (0)
-    if (a_kmajor && b_kmajor) GNN_GEMMW_V(true, true);
-    else if (a_kmajor) GNN_GEMMW_V(true, false);
-    else if (b_kmajor) GNN_GEMMW_V(false, true);
-    else GNN_GEMMW_V(false, false);
-#undef GNN_GEMMW_V
-#undef GNN_GEMMW_LAUNCH
-    GNN_LAUNCHED("gemm_s3w_kernel");
-    if (splits > 1) {
-      const int64_t total = (int64_t)M * N * nbatch;
-      bool vec4 = ldc == N && (M * N) % 4 == 0;
-      for (int b = 0; b < nbatch; ++b) vec4 = vec4 && (uintptr_t)C[b] % 16 == 0;
-      if (vec4) {
-        const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total / 4, (int64_t)256), 2048);
-        gemm_splitk_reduce4_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, M * N, splits, nbatch);
-        GNN_LAUNCHED("gemm_splitk_reduce4_kernel");
-      } else {
-        const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total, (int64_t)256), 2048);
-        gemm_splitk_reduce_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, (int)M, (int)N, ldc, splits, nbatch);
-        GNN_LAUNCHED("gemm_splitk_reduce_kernel");
-      }
-    }
-    return 0;
-  }
-  const int splits = K == 0 ? 1 : pick_splits(M, N, K, split_nbatch > 0 ? split_nbatch : nbatch, slots_of(algo));
-  // XCD-aware tile map for split3 (2-8 % per layer pair, scripts/gemm_bench.py); GNN_GEMM_XCD=0 turns it off
-  int xcdm = 1;
-  if (const char* e = getenv("GNN_GEMM_XCD")) xcdm = atoi(e) != 0;
-  int bkt = algo == ALGO_S3 ? S3_BK : 32;
+  Plan pl = plan_of(algo, M, N, K, nbatch, split_nbatch, batch_index);
+  if (!tail_enabled()) pl.tp = TailPlan{};
+  const TailPlan& tp = pl.tp;
+  l.kern = pl.kern;
+  l.splits = pl.splits;
+  // the kernel's XCD map of a tail launch's whole tiles needs base % 8 == 0 (speed only): tail_plan's
+  // own base is a multiple of 256, so only a product launched alone (batch_index) can turn it off
+  l.xcdm = xcd_map_enabled() && !(tp.s > 0 && tp.base % 8);
+  l.bkt = algo == ALGO_S3 ? S3_BK : 32;
   if (algo == ALGO_F32)
-    if (const char* e = getenv("GNN_GEMM_BKT")) bkt = atoi(e) == 16 ? 16 : 32;  // experiments
-  TailPlan tp;
-  if (algo == ALGO_S3 && splits == 1 && split_nbatch == 0 && K > 0 && tail_enabled()) tp = tail_plan(M, N, K, nbatch);
-  if (algo == ALGO_S3 && splits == 1 && split_nbatch > 0 && nbatch == 1 && batch_index >= 0 && K > 0 &&
-      tail_enabled()) {
-    // one product of a batch of split_nbatch, launched alone: the batch's tail tiles that are this
-    // product's tiles [batch_index * T1, (batch_index + 1) * T1) run as the same k pieces
-    const TailPlan full = tail_plan(M, N, K, split_nbatch);
-    const int64_t T1 = ceil_div(M, (int64_t)BM) * ceil_div(N, (int64_t)BN);
-    const int64_t lo = (int64_t)batch_index * T1;
-    if (full.s > 0 && full.base < lo + T1) {
-      tp.base = (int)std::max<int64_t>(0, full.base - lo);
-      tp.s = full.s;
-      tp.rem = (int)(T1 - tp.base);
-      if (tp.base % 8) xcdm = 0;  // the kernel's XCD map of the whole tiles needs base % 8 == 0 (speed only)
-    }
-  }
-  int klen = splits > 1 ? (int)(ceil_div(ceil_div(K, (int64_t)splits), (int64_t)bkt) * bkt) : (int)K;
-  if (tp.s > 0) klen = (int)(ceil_div(ceil_div(K, (int64_t)tp.s), (int64_t)bkt) * bkt);
-  if (splits > 1 || tp.s > 0) {
-    const size_t need = splits > 1 ? (size_t)splits * nbatch * M * N * sizeof(float) : tail_bytes(tp);
+    if (const char* e = getenv("GNN_GEMM_BKT")) l.bkt = atoi(e) == 16 ? 16 : 32;  // experiments
+  // k ranges: of the tail pieces (tail_plan gives s >= 2 or none), or of the splits
+  const int64_t kpart = tp.s > 0 ? tp.s : l.splits;
+  l.klen = kpart > 1 ? (int)(ceil_div(ceil_div(K, kpart), (int64_t)l.bkt) * l.bkt) : (int)K;
+  if (l.splits > 1 || tp.s > 0) {
+    const size_t need = pl.bytes(M, N, nbatch);
     GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_gemm_f32: workspace too small (%zu < %zu)",
                 workspace_bytes, need);
   }
-  const dim3 grid = tp.s > 0 ? dim3((unsigned)(tp.base + tp.rem * tp.s))
-                             : dim3((unsigned)ceil_div(N, (int64_t)BN), (unsigned)ceil_div(M, (int64_t)BM),
-                                    (unsigned)(nbatch * splits));
-  float* part = (float*)workspace;
-#define GNN_GEMM_LAUNCH(AK, BK, VA, VB)                                                                     \
-  do {                                                                                                        \
-    if (algo == ALGO_S3 && idx)                                                                               \
-      gemm_s3_kernel<AK, BK, VA, VB, true><<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb,  \
-                                                                       ldc, splits, klen, part, abytes, bbytes, \
-                                                                       xcdm, tp.base, tp.s);                    \
-    else if (algo == ALGO_S3)                                                                                 \
-      gemm_s3_kernel<AK, BK, VA, VB><<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb, ldc,  \
-                                                                 splits, klen, part, abytes, bbytes, xcdm,    \
-                                                                 tp.base, tp.s);                              \
-    else if (bkt == 16)                                                                                       \
-      gemm_f32_kernel<AK, BK, VA, VB, 16>                                                                     \
-          <<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb, ldc, splits, klen, part);        \
-    else                                                                                                      \
-      gemm_f32_kernel<AK, BK, VA, VB, 32>                                                                     \
-          <<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, (int)K, lda, ldb, ldc, splits, klen, part);        \
-  } while (0)
-#define GNN_GEMM_V(AK, BK)                                    \
-  do {                                                        \
-    if (va == 4 && vb == 4) GNN_GEMM_LAUNCH(AK, BK, 4, 4);    \
-    else if (va == 4) GNN_GEMM_LAUNCH(AK, BK, 4, 2);          \
-    else if (vb == 4) GNN_GEMM_LAUNCH(AK, BK, 2, 4);          \
-    else GNN_GEMM_LAUNCH(AK, BK, 2, 2);                       \
-  } while (0)
-  if (a_kmajor && b_kmajor) GNN_GEMM_V(true, true);
-  else if (a_kmajor) GNN_GEMM_V(true, false);
-  else if (b_kmajor) GNN_GEMM_V(false, true);
-  else GNN_GEMM_V(false, false);
-#undef GNN_GEMM_V
-#undef GNN_GEMM_LAUNCH
+  l.grid = tp.s > 0 ? dim3((unsigned)(tp.base + tp.rem * tp.s))
+                    : dim3((unsigned)ceil_div(N, (int64_t)(l.kern == KERN_S3W ? W_BN : BN)),
+                           (unsigned)ceil_div(M, (int64_t)BM), (unsigned)(nbatch * l.splits));
+  l.st = (hipStream_t)stream;
+  l.M = (int)M, l.N = (int)N, l.K = (int)K;
+  l.lda = lda, l.ldb = ldb, l.ldc = ldc;
+  l.part = (float*)workspace;
+  l.tail_base = tp.base, l.tail_s = tp.s;
+  if (a_kmajor && b_kmajor) launch_gemm<true, true>(va, vb, l);
+  else if (a_kmajor) launch_gemm<true, false>(va, vb, l);
+  else if (b_kmajor) launch_gemm<false, true>(va, vb, l);
+  else launch_gemm<false, false>(va, vb, l);
   GNN_LAUNCHED(algo == ALGO_S3 ? "gemm_s3_kernel" : "gemm_f32_kernel");
   if (tp.s > 0) {
-    gemm_tail_reduce_kernel<<<dim3((unsigned)(tp.rem * 16)), dim3(256), 0, st>>>(bt, part, (int)M, (int)N, ldc,
-                                                                                tp.base, tp.s);
+    gemm_tail_reduce_kernel<<<dim3((unsigned)(tp.rem * 16)), dim3(256), 0, l.st>>>(bt, l.part, (int)M, (int)N, ldc,
+                                                                                  tp.base, tp.s);
     GNN_LAUNCHED("gemm_tail_reduce_kernel");
   }
-  if (splits > 1) {
-    const int64_t total = (int64_t)M * N * nbatch;
-    bool vec4 = ldc == N && (M * N) % 4 == 0;
-    for (int b = 0; b < nbatch; ++b) vec4 = vec4 && (uintptr_t)C[b] % 16 == 0;
-    if (vec4) {
-      const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total / 4, (int64_t)256), 2048);
-      gemm_splitk_reduce4_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, M * N, splits, nbatch);
-      GNN_LAUNCHED("gemm_splitk_reduce4_kernel");
-    } else {
-      const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total, (int64_t)256), 2048);
-      gemm_splitk_reduce_kernel<<<dim3(g), dim3(256), 0, st>>>(bt, part, (int)M, (int)N, ldc, splits, nbatch);
-      GNN_LAUNCHED("gemm_splitk_reduce_kernel");
-    }
-  }
+  if (l.splits > 1) return launch_splitk_reduce(bt, l.part, M, N, ldc, l.splits, nbatch, l.st);
   return 0;
-}
-
-size_t workspace_bytes_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch) {
-  if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return 0;
-  if (algo == ALGO_S3 && use_wide(M, N, K, nbatch)) {
-    const int s = pick_splits_wide(M, N, K, nbatch);
-    return s > 1 ? (size_t)s * nbatch * M * N * sizeof(float) : 0;
-  }
-  const int s = pick_splits(M, N, K, nbatch, slots_of(algo));
-  if (s > 1) return (size_t)s * nbatch * M * N * sizeof(float);
-  return algo == ALGO_S3 ? tail_bytes(tail_plan(M, N, K, nbatch)) : 0;  // whatever GNN_GEMM_TAIL says
 }
 
 }  // namespace
@@ -1366,7 +1159,7 @@ int gnn_gemm_p3(int64_t M, int64_t N, int64_t K, int nbatch, const void* const* 
   hipStream_t st = (hipStream_t)stream;
   const int Mp = (int)(ceil_div(M, (int64_t)128) * 128), Np = (int)(ceil_div(N, (int64_t)128) * 128);
   const int KT = (int)ceil_div(K, (int64_t)16);
-  const int splits = K == 0 ? 1 : pick_splits(M, N, K, nbatch, SLOTS_S3);
+  const int splits = K == 0 ? 1 : pick_splits(M, N, K, nbatch, BN, SLOTS_S3);
   // the split3 kernel's k ranges: ceil(ceil(K / splits) / 16) k tiles per split
   const int ktlen = splits > 1 ? (int)ceil_div(ceil_div(K, (int64_t)splits), (int64_t)S3_BK) : KT;
   if (splits > 1) {
@@ -1374,27 +1167,15 @@ int gnn_gemm_p3(int64_t M, int64_t N, int64_t K, int nbatch, const void* const* 
     GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_gemm_p3: workspace too small (%zu < %zu)", workspace_bytes,
                 need);
   }
-  int xcdm = 1;
-  if (const char* e = getenv("GNN_GEMM_XCD")) xcdm = atoi(e) != 0;
   const dim3 grid((unsigned)(Np / BN), (unsigned)(Mp / BM), (unsigned)(nbatch * splits));
   float* part = (float*)workspace;
-  gemm_p3_kernel<<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, Mp, Np, KT, ldc, splits, ktlen, part, xcdm);
+  gemm_p3_kernel<<<grid, dim3(256), 0, st>>>(bt, (int)M, (int)N, Mp, Np, KT, ldc, splits, ktlen, part,
+                                             (int)xcd_map_enabled());
   GNN_LAUNCHED("gemm_p3_kernel");
   if (splits > 1) {
     Batch cb{};
     for (int b = 0; b < nbatch; ++b) cb.C[b] = C[b];
-    const int64_t total = (int64_t)M * N * nbatch;
-    bool vec4 = ldc == N && (M * N) % 4 == 0;
-    for (int b = 0; b < nbatch; ++b) vec4 = vec4 && (uintptr_t)C[b] % 16 == 0;
-    if (vec4) {
-      const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total / 4, (int64_t)256), 2048);
-      gemm_splitk_reduce4_kernel<<<dim3(g), dim3(256), 0, st>>>(cb, part, M * N, splits, nbatch);
-      GNN_LAUNCHED("gemm_splitk_reduce4_kernel");
-    } else {
-      const unsigned g = (unsigned)std::min<int64_t>(ceil_div(total, (int64_t)256), 2048);
-      gemm_splitk_reduce_kernel<<<dim3(g), dim3(256), 0, st>>>(cb, part, (int)M, (int)N, ldc, splits, nbatch);
-      GNN_LAUNCHED("gemm_splitk_reduce_kernel");
-    }
+    return launch_splitk_reduce(cb, part, M, N, ldc, splits, nbatch, st);
   }
   return 0;
 }

@@ -119,6 +119,32 @@ def test_workspace_and_config():
     assert L.gnn_segsort_workspace_bytes(100) >= 800
 
 
+_GEMM_WS_SHAPES = [(512, 602, 15809, 2), (512, 1024, 8689, 2), (15809, 512, 602, 2), (8689, 512, 1024, 2),
+                   (8689, 1024, 512, 2), (101, 131, 3001, 1), (1, 5, 3, 1)]
+# per shape: (gnn_gemm_f32_, gnn_gemm_f32_split3_, gnn_gemm_p3_)workspace_bytes, recorded from the library
+# before the split3 kernels were folded into one template (the query is a pure function of the shape,
+# the batch count and GNN_GEMM_WIDE / GNN_GEMM_SPLITS; GNN_GEMM_TAIL does not change it)
+_GEMM_WS_DEFAULT = [(29589504, 46850048, 46850048), (33554432, 50331648, 50331648), (0, 0, 0),
+                    (0, 8388608, 8388608), (0, 0, 0), (582164, 582164, 582164), (0, 0, 0)]
+_GEMM_WS_WIDE1 = [(29589504, 51781632, 51781632), (33554432, 67108864, 67108864), (0, 0, 0), (0, 0, 0), (0, 0, 0),
+                  (582164, 582164, 582164), (0, 0, 0)]
+
+
+@pytest.mark.parametrize("env,expected", [({}, _GEMM_WS_DEFAULT), ({"GNN_GEMM_WIDE": "1"}, _GEMM_WS_WIDE1),
+                                          ({"GNN_GEMM_WIDE": "-1"}, _GEMM_WS_DEFAULT),
+                                          ({"GNN_GEMM_TAIL": "0"}, _GEMM_WS_DEFAULT)])
+def test_gemm_workspace_query(monkeypatch, env, expected):
+    L = _lib.lib()
+    for k in ("GNN_GEMM_WIDE", "GNN_GEMM_TAIL", "GNN_GEMM_SPLITS"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for shape, want in zip(_GEMM_WS_SHAPES, expected):
+        got = (L.gnn_gemm_f32_workspace_bytes(*shape), L.gnn_gemm_f32_split3_workspace_bytes(*shape),
+               L.gnn_gemm_p3_workspace_bytes(*shape))
+        assert got == want, (env, shape)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

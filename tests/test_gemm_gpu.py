@@ -51,6 +51,8 @@ def test_gemm_split_k_and_batch(dev, algo):
     # weight-gradient shape: small output, long reduction -> split over k, two problems batched
     _check(True, True, 512, 602, 5000, 2, dev, algo=algo)
     _check(True, True, 100, 130, 3001, 3, dev, algo=algo)
+    # M·N odd: the split sums take the scalar reduce kernel (two tiles, 11 splits)
+    _check(True, True, 101, 131, 3001, 1, dev, algo=algo)
 
 
 @pytest.mark.parametrize("algo", GEMM_ALGOS)
@@ -166,7 +168,8 @@ def test_split3_indexed_rejects_bad_layouts(dev):
 
 
 @pytest.mark.parametrize("a_km,b_km,M,N,K,nb", [(False, False, 300, 200, 70, 2), (True, True, 130, 257, 4000, 2),
-                                                (False, True, 129, 512, 33, 1), (True, False, 64, 64, 16, 1)])
+                                                (False, True, 129, 512, 33, 1), (True, False, 64, 64, 16, 1),
+                                                (True, True, 101, 131, 3001, 1)])
 def test_p3_packed_equals_split3(dev, a_km, b_km, M, N, K, nb):
     """gnn_gemm_p3 over operands packed once into their bf16 pieces (gnn_gemm_p3_pack_f32, also
     through a row index) is bit-identical to gnn_gemm_f32_split3 on the same operands (same pieces,
@@ -231,7 +234,7 @@ def test_split3_tail_tiles(dev, monkeypatch):
 
 @pytest.mark.parametrize("a_km,b_km", [(False, False), (False, True), (True, True), (True, False)])
 @pytest.mark.parametrize("M,N,K,nb", [(300, 256, 77, 1), (130, 513, 602, 2), (257, 700, 1024, 1), (512, 602, 5000, 2),
-                                      (1000, 512, 33, 2)])
+                                      (1000, 512, 33, 2), (101, 131, 3001, 1)])
 def test_split3_wide_fp64_bound_and_whole_tiles_bit_identical(dev, monkeypatch, a_km, b_km, M, N, K, nb):
     """The wide split3 kernel (GNN_GEMM_WIDE=1: 128 x 256 tiles, a wave owns 64 x 128) within the fp64
     bound on every layout, edge tiles, split-k and batches; where it runs k unsplit (every shape
