@@ -47,6 +47,9 @@ _SIGNATURES = {
     "gnn_csr_transpose": (_INT, [_VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "gnn_gather_rows_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP]),
     "gnn_gather_rows2_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP]),
+    "gnn_gather_rows_h16_f32": (_INT, [_VP, _I64, _INT, _VP, _VP, _I64, _VP, _I64, _I64, _VP]),
+    "gnn_gather_rows2_h16_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _INT, _VP, _I64, _I64,
+                                        _VP]),
     "gnn_gather_rows_host_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP]),
     "gnn_host_register": (_INT, [_VP, _SZ]),
     "gnn_host_unregister": (_INT, [_VP]),
@@ -140,6 +143,8 @@ _SAMPLER_SIGNATURES = {
     "gnn_mt19937_random_sample": (_INT, [ctypes.c_uint32, _I64, _VP]),
     "gnn_sampler_profile": (_INT, [_VP, ctypes.c_int32, ctypes.c_int32]),
     "gnn_host_gather_rows_f32": (_INT, [_VP, _I64, _I64, _VP, _I64, _I64, _VP, _I64]),
+    "gnn_host_gather_rows_b16": (_INT, [_VP, _I64, _I64, _VP, _I64, _I64, _VP, _I64]),
+    "gnn_loader_set_feat_b16": (_INT, [_VP, _VP, _I64, _I64, _I64, ctypes.c_int32]),
     "gnn_loader_create": (_VP, [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _VP, ctypes.c_int32, ctypes.c_int32,
                                 _VP, _VP, _I64, _I64, _I64, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP,
                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

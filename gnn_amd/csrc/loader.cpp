@@ -150,6 +150,10 @@ struct gnn_loader {
   std::vector<int64_t> devices;
   const float* feat;
   int64_t ld_feat, F, ld_x0;
+  // a 16-bit table instead (gnn_loader_set_feat_b16): host_rows are ld_rows 2-byte elements wide
+  const uint16_t* feat16 = nullptr;
+  int64_t ld_rows = 0;
+  int32_t feat_kind = 0;
   std::vector<int64_t> samp;
   std::vector<int32_t> orders;
   int32_t kind, device_extract, csc_from;
@@ -191,6 +195,18 @@ inline void copy_row_nt(float* dst, const float* src, int64_t F, int64_t ld) {
   for (; c < ld; c += 4) {
     alignas(16) float t[4];
     for (int k = 0; k < 4; ++k) t[k] = c + k < F ? src[c + k] : 0.0f;
+    _mm_stream_si128(reinterpret_cast<__m128i*>(dst + c), _mm_load_si128(reinterpret_cast<const __m128i*>(t)));
+  }
+}
+
+// The same for a row of 2-byte elements (ld a multiple of 8, dst 16-byte aligned).
+inline void copy_row_nt16(uint16_t* dst, const uint16_t* src, int64_t F, int64_t ld) {
+  int64_t c = 0;
+  for (; c + 8 <= F; c += 8)
+    _mm_stream_si128(reinterpret_cast<__m128i*>(dst + c), _mm_loadu_si128(reinterpret_cast<const __m128i*>(src + c)));
+  for (; c < ld; c += 8) {
+    alignas(16) uint16_t t[8];
+    for (int k = 0; k < 8; ++k) t[k] = c + k < F ? src[c + k] : (uint16_t)0;
     _mm_stream_si128(reinterpret_cast<__m128i*>(dst + c), _mm_load_si128(reinterpret_cast<const __m128i*>(t)));
   }
 }
@@ -263,7 +279,10 @@ void fill(gnn_loader& ld, const gnn_ladies_result& res, const Job& job, gnn_batc
   }
   const int bb = GNN_BLOB_HEADER + nl * GNN_BLOB_LAYER_SLOTS;
   secs.push_back({bb + GNN_B_LABELS, bs * ld.C, 4});
-  secs.push_back({bb + GNN_B_HOST_ROWS, ld.feat ? (int64_t)host_src.size() * ld.ld_x0 : 0, 4});
+  if (ld.feat16)
+    secs.push_back({bb + GNN_B_HOST_ROWS, (int64_t)host_src.size() * ld.ld_rows, 2});
+  else
+    secs.push_back({bb + GNN_B_HOST_ROWS, ld.feat ? (int64_t)host_src.size() * ld.ld_x0 : 0, 4});
   secs.push_back({bb + GNN_B_OWN_POS, (int64_t)own_pos.size(), 8});
   secs.push_back({bb + GNN_B_OWN_SRC, (int64_t)own_src.size(), 8});
   secs.push_back({bb + GNN_B_HOST_POS, (int64_t)host_pos.size(), 8});
@@ -350,6 +369,28 @@ void fill(gnn_loader& ld, const gnn_ladies_result& res, const Job& job, gnn_batc
       }
     }
     if (nt) _mm_sfence();  // the stores are visible before the batch is handed over
+  } else if (ld.feat16) {  // a 16-bit table: the same copy on 2-byte elements, ld_rows wide
+    uint16_t* rows = (uint16_t*)at(bb + GNN_B_HOST_ROWS);
+    const bool nt = ld.ld_rows % 8 == 0 && (uintptr_t)rows % 16 == 0 && !getenv_off("GNN_LOADER_NT");
+    constexpr size_t kAhead = 4;
+    for (size_t i = 0; i < host_src.size(); ++i) {
+      if (i + kAhead < host_src.size()) {
+        const char* p = reinterpret_cast<const char*>(ld.feat16 + host_src[i + kAhead] * ld.ld_feat);
+        _mm_prefetch(p, _MM_HINT_T0);
+        _mm_prefetch(p + 64, _MM_HINT_T0);
+      }
+      uint16_t* dst = rows + (int64_t)i * ld.ld_rows;
+      const uint16_t* src = ld.feat16 + host_src[i] * ld.ld_feat;
+      if (nt) {
+        copy_row_nt16(dst, src, ld.F, ld.ld_rows);
+      } else {
+        std::memcpy(dst, src, (size_t)ld.F * 2);
+        if (ld.ld_rows > ld.F) std::memset(dst + ld.F, 0, (size_t)(ld.ld_rows - ld.F) * 2);
+      }
+    }
+    if (nt) _mm_sfence();
+    d[GNN_H_FEAT_KIND] = ld.feat_kind;
+    d[GNN_H_LD_HOST_ROWS] = ld.ld_rows;
   }
   d[GNN_H_VERSION] = GNN_BLOB_VERSION;
   d[GNN_H_LAYERS] = nl;
@@ -515,6 +556,29 @@ int gnn_loader_set_colcount_workers(gnn_loader* ld, int32_t workers) {
     return -22;
   }
   ld->cc_workers = workers;
+  return 0;
+}
+
+int gnn_loader_set_feat_b16(gnn_loader* ld, const void* feat, int64_t ld_feat, int64_t F, int64_t ld_rows,
+                            int32_t kind) {
+  if (!ld || !feat || (kind != 1 && kind != 2) || F < 0 || F > ld_feat || F > ld_rows || (uintptr_t)feat % 2) {
+    gnn_smp::set_error("gnn_loader_set_feat_b16: bad arguments (kind 1 = fp16, 2 = bf16; F <= ld_feat, ld_rows)");
+    return -22;
+  }
+  std::lock_guard<std::mutex> lk(ld->mu);
+  if (ld->feat || F != ld->F || ld_rows < ld->ld_x0) {
+    gnn_smp::set_error(
+        "gnn_loader_set_feat_b16: the loader has an fp32 table, another F, or ld_rows below its ld_x0");
+    return -22;
+  }
+  if (ld->next_id != 0) {
+    gnn_smp::set_error("gnn_loader_set_feat_b16: batches already submitted");
+    return -22;
+  }
+  ld->feat16 = static_cast<const uint16_t*>(feat);
+  ld->ld_feat = ld_feat;
+  ld->ld_rows = ld_rows;
+  ld->feat_kind = kind;
   return 0;
 }
 

@@ -1053,4 +1053,19 @@ int gnn_host_gather_rows_f32(const float* src, int64_t ld_src, int64_t num_src_r
   return 0;
 }
 
+int gnn_host_gather_rows_b16(const void* src, int64_t ld_src, int64_t num_src_rows, const int64_t* idx, int64_t n,
+                             int64_t F, void* dst, int64_t ld_dst) {
+  if (n < 0 || F < 0 || F > ld_src || F > ld_dst || (n > 0 && (!src || !idx || !dst)))
+    return fail("gnn_host_gather_rows_b16: bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || idx[i] >= num_src_rows) return fail("gnn_host_gather_rows_b16: index %lld out of range", (long long)idx[i]);
+  const uint16_t* s = static_cast<const uint16_t*>(src);
+  for (int64_t i = 0; i < n; ++i) {
+    uint16_t* d = static_cast<uint16_t*>(dst) + i * ld_dst;
+    std::memcpy(d, s + idx[i] * ld_src, (size_t)F * sizeof(uint16_t));
+    if (ld_dst > F) std::memset(d + F, 0, (size_t)(ld_dst - F) * sizeof(uint16_t));
+  }
+  return 0;
+}
+
 }  // extern "C"

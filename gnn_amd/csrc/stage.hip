@@ -6,7 +6,8 @@
 // to_device, sampler.DeviceBatch.build_operands): 0.2-0.3 ms per step, doubling when the host
 // runs slow. Here the training thread makes two calls (plan, stage) and this file issues, on the
 // staging stream, the library calls the Python path made, with the same arguments:
-//   blob upload -> [gate] -> X0 gather (own-buffer + host rows, gnn_gather_rows2_f32) ->
+//   blob upload -> [gate] -> X0 gather (own-buffer + host rows, gnn_gather_rows2_f32; from a
+//   16-bit feature store, GNN_ST_FEAT_KIND, the widening gnn_gather_rows2_h16_f32) ->
 //   per layer: gnn_ladies_extract_f32 (GPU-extracted) | gnn_build_operand_sorted_f32 (+ _t on the
 //   blob's CSC) -> the extraction error flag into pinned host memory.
 // No kernels of its own; nothing allocated (the caller's arena holds every output and the
@@ -75,6 +76,12 @@ size_t plan(const int64_t* a, int64_t* out) {
   if (d[GNN_H_VERSION] != GNN_BLOB_VERSION || d[GNN_H_LAYERS] < 0 || d[GNN_H_LAYERS] > GNN_BLOB_MAX_LAYERS) {
     gnn::fail(GNN_EINVAL, "gnn_stage: blob version %lld / layers %lld", (long long)d[GNN_H_VERSION],
               (long long)d[GNN_H_LAYERS]);
+    return 0;
+  }
+  const int64_t kind = a[GNN_ST_FEAT_KIND];
+  if ((kind != GNN_FEAT_F32 && kind != GNN_FEAT_F16 && kind != GNN_FEAT_BF16) || kind != d[GNN_H_FEAT_KIND]) {
+    gnn::fail(GNN_EINVAL, "gnn_stage: feature kind %lld does not match the blob's %lld (0 fp32, 1 fp16, 2 bf16)",
+              (long long)kind, (long long)d[GNN_H_FEAT_KIND]);
     return 0;
   }
   BlobView b{d, AP<const char>(a, GNN_ST_HOST_BLOB), nullptr, (int)d[GNN_H_LAYERS]};
@@ -162,13 +169,22 @@ int gnn_stage_batch_f32(const int64_t* a, void* stream) {
   float* x0 = AP<float>(a, GNN_ST_X0);
   GNN_REQUIRE(x0 && ld_x0 == d[GNN_H_LD_X0], "gnn_stage_batch_f32: X0 NULL or its stride %lld != the blob's %lld",
               (long long)ld_x0, (long long)d[GNN_H_LD_X0]);
-  GNN_REQUIRE(nh == 0 || b.count(B + GNN_B_HOST_ROWS) == nh * ld_x0,
+  const int kind = (int)a[GNN_ST_FEAT_KIND];  // equals the blob's (plan)
+  const int64_t ld_host = kind == GNN_FEAT_F32 ? ld_x0 : d[GNN_H_LD_HOST_ROWS];
+  GNN_REQUIRE(nh == 0 || b.count(B + GNN_B_HOST_ROWS) == nh * ld_host,
               "gnn_stage_batch_f32: the blob holds no host rows (zero-copy batches stage through Python)");
   GNN_REQUIRE(n_own == 0 || a[GNN_ST_BUFFER], "gnn_stage_batch_f32: NULL feature buffer");
-  GNN_STAGE_TRY(gnn_gather_rows2_f32(AP<const float>(a, GNN_ST_BUFFER), a[GNN_ST_LD_BUFFER],
-                               b.dv<const int64_t>(B + GNN_B_OWN_SRC), b.dv<const int64_t>(B + GNN_B_OWN_POS), n_own,
-                               nh ? b.dv<const float>(B + GNN_B_HOST_ROWS) : x0, ld_x0, nullptr,
-                               b.dv<const int64_t>(B + GNN_B_HOST_POS), nh, x0, ld_x0, a[GNN_ST_F], stream));
+  if (kind == GNN_FEAT_F32)
+    GNN_STAGE_TRY(gnn_gather_rows2_f32(AP<const float>(a, GNN_ST_BUFFER), a[GNN_ST_LD_BUFFER],
+                                 b.dv<const int64_t>(B + GNN_B_OWN_SRC), b.dv<const int64_t>(B + GNN_B_OWN_POS), n_own,
+                                 nh ? b.dv<const float>(B + GNN_B_HOST_ROWS) : x0, ld_x0, nullptr,
+                                 b.dv<const int64_t>(B + GNN_B_HOST_POS), nh, x0, ld_x0, a[GNN_ST_F], stream));
+  else  // a 16-bit store: the same gather, widening (the sources' strides are their own)
+    GNN_STAGE_TRY(gnn_gather_rows2_h16_f32(AP<const void>(a, GNN_ST_BUFFER), a[GNN_ST_LD_BUFFER],
+                                     b.dv<const int64_t>(B + GNN_B_OWN_SRC), b.dv<const int64_t>(B + GNN_B_OWN_POS),
+                                     n_own, nh ? b.dv<const void>(B + GNN_B_HOST_ROWS) : nullptr, ld_host, nullptr,
+                                     b.dv<const int64_t>(B + GNN_B_HOST_POS), nh, kind, x0, ld_x0, a[GNN_ST_F],
+                                     stream));
   // 3. the operands
   const int64_t csc_from = a[GNN_ST_CSC_FROM];
   const int64_t ws_off = b.nl > 0 ? out[GNN_SO_WORKSPACE] : -1;

@@ -508,6 +508,11 @@ def create_coo_tensor(fullrowptr, rowptr, colidx, normfact, nrows, ncols) -> tor
     return t
 
 
+# element kind of a feature store's rows (include/gnn_spmm.h GNN_FEAT_*)
+FEAT_F32, FEAT_F16, FEAT_BF16 = 0, 1, 2
+FEAT_KIND = {torch.float32: FEAT_F32, torch.float16: FEAT_F16, torch.bfloat16: FEAT_BF16}
+
+
 def _padded_width(src: torch.Tensor, dst: torch.Tensor, F: int) -> int:
     """Rows of a 602-wide layer live in 608-float (whole 128-byte line) rows: when both row
     strides are multiples of 4 and every row's storage holds the padded width, copy F rounded
@@ -526,13 +531,17 @@ def _padded_width(src: torch.Tensor, dst: torch.Tensor, F: int) -> int:
 
 def gather_rows(src: torch.Tensor, src_idx: Optional[torch.Tensor], dst: torch.Tensor,
                 dst_idx: Optional[torch.Tensor], n: Optional[int] = None) -> None:
-    """dst[dst_idx] = src[src_idx] row copy on the GPU (int64 indices, fp32 rows)."""
+    """dst[dst_idx] = src[src_idx] row copy on the GPU (int64 indices; fp32 rows, or fp16 / bf16
+    source rows widened exactly into the fp32 destination: gnn_gather_rows_h16_f32)."""
     _require(src.is_cuda and dst.is_cuda, "gather_rows tensors must be CUDA tensors")
-    _require(src.dtype == torch.float32 and dst.dtype == torch.float32, "gather_rows tensors must be float32")
+    _require(src.dtype in FEAT_KIND and dst.dtype == torch.float32,
+             "gather_rows: source must be float32, float16 or bfloat16, destination float32")
     _require(src.stride(1) == 1 and dst.stride(1) == 1, "gather_rows rows must be contiguous")
+    kind = FEAT_KIND[src.dtype]
     F = dst.shape[1]
     _require(src.shape[1] >= F, "gather_rows: source rows narrower than destination")
-    F = _padded_width(src, dst, F)
+    if kind == FEAT_F32:
+        F = _padded_width(src, dst, F)
     if n is None:
         n = int((src_idx if src_idx is not None else dst_idx).numel()) if (src_idx is not None or dst_idx is not None) \
             else int(src.shape[0])
@@ -541,6 +550,11 @@ def gather_rows(src: torch.Tensor, src_idx: Optional[torch.Tensor], dst: torch.T
             _require(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), "gather_rows indices must be int64 CUDA")
     dev = dst.device
     with _lib.on_device(dev):
+        if kind != FEAT_F32:
+            _lib.check(_lib.lib().gnn_gather_rows_h16_f32(src.data_ptr(), src.stride(0), kind, _ptr(src_idx),
+                                                          dst.data_ptr(), dst.stride(0), _ptr(dst_idx), n, F,
+                                                          _stream(dev)), "gnn_gather_rows_h16_f32")
+            return
         _lib.check(_lib.lib().gnn_gather_rows_f32(src.data_ptr(), src.stride(0), _ptr(src_idx), dst.data_ptr(),
                                                   dst.stride(0), _ptr(dst_idx), n, F, _stream(dev)),
                    "gnn_gather_rows_f32")
@@ -550,17 +564,27 @@ def gather_rows2(src0: torch.Tensor, idx0: Optional[torch.Tensor], pos0: Optiona
                  src1: torch.Tensor, idx1: Optional[torch.Tensor], pos1: Optional[torch.Tensor], n1: int,
                  dst: torch.Tensor) -> None:
     """dst[pos0] = src0[idx0] (n0 rows) and dst[pos1] = src1[idx1] (n1 rows) in one launch
-    (gnn_gather_rows2_f32): X0's own-buffer and host rows."""
+    (gnn_gather_rows2_f32): X0's own-buffer and host rows. Both sources float32, or both float16
+    / both bfloat16 (gnn_gather_rows2_h16_f32, widening); dst is float32."""
+    _require(src0.dtype in FEAT_KIND and src1.dtype == src0.dtype and dst.dtype == torch.float32,
+             "gather_rows2: sources must share one of float32 / float16 / bfloat16, destination float32")
     for t in (src0, src1, dst):
-        _require(t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1,
-                 "gather_rows2 tensors must be float32 CUDA tensors with contiguous rows")
+        _require(t.is_cuda and t.stride(1) == 1, "gather_rows2 tensors must be CUDA tensors with contiguous rows")
+    kind = FEAT_KIND[src0.dtype]
     for t in (idx0, pos0, idx1, pos1):
         if t is not None:
             _require(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), "gather_rows2 indices must be int64 CUDA")
     F = dst.shape[1]
     _require(src0.shape[1] >= F and src1.shape[1] >= F, "gather_rows2: source rows narrower than destination")
-    F = min(_padded_width(src0, dst, F), _padded_width(src1, dst, F))
     dev = dst.device
+    if kind != FEAT_F32:
+        with _lib.on_device(dev):
+            _lib.check(_lib.lib().gnn_gather_rows2_h16_f32(src0.data_ptr(), src0.stride(0), _ptr(idx0), _ptr(pos0),
+                                                           int(n0), src1.data_ptr(), src1.stride(0), _ptr(idx1),
+                                                           _ptr(pos1), int(n1), kind, dst.data_ptr(), dst.stride(0),
+                                                           F, _stream(dev)), "gnn_gather_rows2_h16_f32")
+        return
+    F = min(_padded_width(src0, dst, F), _padded_width(src1, dst, F))
     with _lib.on_device(dev):
         _lib.check(_lib.lib().gnn_gather_rows2_f32(src0.data_ptr(), src0.stride(0), _ptr(idx0), _ptr(pos0), int(n0),
                                                    src1.data_ptr(), src1.stride(0), _ptr(idx1), _ptr(pos1), int(n1),

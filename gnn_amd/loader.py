@@ -182,6 +182,7 @@ class BatchLoader:
 # descriptor layout (mirrors GNN_BLOB_* / GNN_H_* / GNN_L_* / GNN_B_* of gnn_sampler.h)
 BLOB_VERSION, BLOB_HEADER, BLOB_LAYER_SLOTS, BLOB_BATCH_SLOTS = 1, 16, 32, 16
 H_VERSION, H_LAYERS, H_BYTES, H_BATCH, H_CLASSES, H_INPUTS, H_WORLD, H_LD_X0, H_SEED, H_PINNED = range(10)
+H_FEAT_KIND, H_LD_HOST_ROWS = 10, 11  # 16-bit host rows (both 0: fp32 rows, ld_x0 wide)
 (L_PRESENT, L_ON_DEVICE, L_M, L_K, L_NNZ, L_SNUM, L_NSAMPLED, L_HAS_RMAP) = range(8)
 L_FULLROWPTR, L_ROWPTR, L_COLIDX, L_NORMFACT, L_CSC_COLPTR, L_CSC_ROWS, L_ROWS, L_COLS, L_SAMPLED, L_RMAP, \
     L_COLSEG = range(8, 30, 2)
@@ -192,9 +193,11 @@ STAGE_SLOTS, STAGE_OUT_SLOTS, BLOB_MAX_LAYERS = 24, 6, 16
 (ST_DESC, ST_HOST_BLOB, ST_DEV_BLOB, ST_UPLOAD, ST_BUFFER, ST_LD_BUFFER, ST_X0, ST_LD_X0, ST_F, ST_INDPTR, ST_INDICES,
  ST_DEGREE, ST_NUM_NODES, ST_INDPTR_T, ST_INDICES_T, ST_ERR, ST_ERR_HOST, ST_GATE, ST_CSC_FROM, ST_ARENA,
  ST_ARENA_BYTES) = range(21)
+ST_FEAT_KIND = 21
 SO_ROWPTR, SO_COL, SO_VAL, SO_ROWS_T, SO_VAL_T = range(5)
 _I32, _I64, _F32 = np.dtype(np.int32), np.dtype(np.int64), np.dtype(np.float32)
 _TDT = {_I32: torch.int32, _I64: torch.int64, _F32: torch.float32}
+_KIND_TDT = {1: torch.float16, 2: torch.bfloat16}  # GNN_H_FEAT_KIND of 16-bit host rows
 
 
 def _release_blob(release, handle, uploads) -> None:
@@ -333,8 +336,14 @@ class NativeBatch:
         """(own_pos, own_src, host_pos, host rows | host_src) on the device for Stager.issue."""
         self.device_blob(dev)
         bb = self._bb
-        ld = int(self.desc[H_LD_X0])
-        rows = self._d(bb + B_HOST_ROWS, _F32)
+        kind = int(self.desc[H_FEAT_KIND])
+        if kind:  # 16-bit host rows, GNN_H_LD_HOST_ROWS elements wide
+            ld = int(self.desc[H_LD_HOST_ROWS])
+            off, cnt = int(self.desc[bb + B_HOST_ROWS]), self._count(bb + B_HOST_ROWS)
+            rows = self._dev[1][off:off + cnt * 2].view(_KIND_TDT[kind])
+        else:
+            ld = int(self.desc[H_LD_X0])
+            rows = self._d(bb + B_HOST_ROWS, _F32)
         host = rows.view(-1, ld) if self._count(bb + B_HOST_ROWS) else self._d(bb + B_HOST_SRC, _I64)
         return (self._d(bb + B_OWN_POS, _I64), self._d(bb + B_OWN_SRC, _I64), self._d(bb + B_HOST_POS, _I64), host)
 
@@ -366,6 +375,7 @@ class NativeBatch:
         a[ST_DESC], a[ST_HOST_BLOB], a[ST_DEV_BLOB], a[ST_UPLOAD] = desc.ctypes.data, self.ptr, blob.data_ptr(), upload
         buf = store.gpu_buffer
         a[ST_BUFFER], a[ST_LD_BUFFER] = buf.data_ptr(), buf.stride(0)
+        a[ST_FEAT_KIND] = store.kind  # 16-bit stores: the widening gather; checked against the blob's kind
         a[ST_X0], a[ST_LD_X0], a[ST_F] = x0.data_ptr(), x0.stride(0), x0.shape[1]
         err_host = None
         if graph is not None:
@@ -535,12 +545,17 @@ class NativeLoader:
             orders=np.ascontiguousarray(orders, dtype=np.int32),
             p=g.fastgcn_p if kind == "fastgcn" else None)
         feat, ld_feat, F, ld_x0 = None, 0, 0, 0
+        feat16 = None  # a 16-bit table goes in by gnn_loader_set_feat_b16 after the create
         if store is not None:
             F, ld_x0 = store.F, store.ld
             if not store.zero_copy:
                 host = store.host
-                assert host.dtype == torch.float32 and host.stride(1) == 1
-                feat, ld_feat = host.data_ptr(), host.stride(0)
+                if host.dtype != store.dtype or host.stride(1) != 1:
+                    raise ValueError("NativeLoader: the store's host table must have contiguous rows of its dtype")
+                if store.kind == 0:
+                    feat, ld_feat = host.data_ptr(), host.stride(0)
+                else:
+                    feat16 = host
                 self._keep["feat"] = host
         k = self._keep
         ptr = lambda a: None if a is None else a.ctypes.data
@@ -556,6 +571,9 @@ class NativeLoader:
             ptr(k["p"]), dx, 1, self.workers, int(bool(pinned)))
         if not self.handle:
             raise RuntimeError("gnn_loader_create failed: " + L.gnn_sampler_last_error().decode(errors="replace"))
+        if feat16 is not None:
+            _lib.check_sampler(L.gnn_loader_set_feat_b16(self.handle, feat16.data_ptr(), feat16.stride(0), F,
+                                                         store.ld_rows, store.kind), "gnn_loader_set_feat_b16")
         self.device_count = device_count is not None and kind == "ladies" and g.data is None
         self.device_count_workers = 0
         if self.device_count:

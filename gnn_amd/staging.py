@@ -28,6 +28,10 @@ Here (DESIGN.md §Feature staging):
       peer): RCCL all-to-all — the request sizes and slot ids are negotiated on the host over a
       gloo group (no GPU sync), each rank gathers the rows its peers asked for from its own
       buffer, one all_to_all_single moves them over xGMI, and a scatter kernel places them.
+  * 16-bit tables (float16 / bfloat16; the reference's MAG240M features, preprocess.py:112):
+    buffer, pinned host rows and peer rows keep the table's dtype and every gather above widens
+    to fp32 on the way (gnn_gather_rows_h16_f32 / gnn_gather_rows2_h16_f32) — main.py:132-134's
+    ``.float()``, exact, so X0 is ``feats.float()[input_nodes]`` bit for bit.
 """
 from __future__ import annotations
 
@@ -99,15 +103,30 @@ class FeatureStore:
     ``zero_copy``: the host table is kept in ld-wide rows, pinned and mapped for the device
     (gnn_host_register); the GPU then reads a batch's non-buffered rows straight from it over
     PCIe (gnn_gather_rows_host_f32 on the staging stream) and no host thread copies rows.
-    Otherwise the batch producer gathers them into a pinned buffer for one hipMemcpyAsync."""
+    Otherwise the batch producer gathers them into a pinned buffer for one hipMemcpyAsync.
+
+    The table may be float32, float16 or bfloat16 (``dtype``; ``kind`` is its GNN_FEAT_* code). A
+    16-bit table (MAG240M's paper_feat, preprocess.py:112) stays 16-bit in the GPU buffer, the
+    pinned host rows and over the peer links; the X0 gathers widen it (exactly) to fp32, the
+    ``.float()`` of main.py:132-134. ``ld`` is X0's stride in floats either way; ``ld_rows`` is
+    the stride of buffer and host rows in their own elements: ``ld`` for fp32, F rounded up to 64
+    (whole 128-byte lines, never below ``ld``) for 16-bit stores."""
 
     def __init__(self, feat_data: torch.Tensor, buffer_nodes: np.ndarray, device, rank: int = 0,
                  pin_host: bool = False, zero_copy: bool = False):
-        assert feat_data.dtype == torch.float32 and feat_data.dim() == 2
+        if feat_data.dtype not in cso.FEAT_KIND or feat_data.dim() != 2:
+            raise ValueError("FeatureStore: the feature table must be a 2-D float32, float16 or bfloat16 tensor, "
+                             f"got {feat_data.dtype} with {feat_data.dim()} dimensions")
+        self.dtype = feat_data.dtype
+        self.kind = cso.FEAT_KIND[self.dtype]
+        if zero_copy and self.kind != cso.FEAT_F32:
+            raise ValueError(f"FeatureStore(zero_copy=True) reads fp32 tables only (got {self.dtype}): "
+                             "16-bit stores stage through the pinned host-row copy")
         self.device = torch.device(device)
         self.rank = rank
         self.F = int(feat_data.shape[1])
         self.ld = padded_ld(self.F)
+        self.ld_rows = self.ld if self.kind == cso.FEAT_F32 else max(padded_ld(self.F, 64), self.ld)
         self.zero_copy = bool(zero_copy)
         if self.zero_copy:
             from . import _lib
@@ -123,24 +142,26 @@ class FeatureStore:
         else:
             self.host = feat_data.pin_memory() if pin_host else feat_data.contiguous()
         idx = torch.from_numpy(np.asarray(buffer_nodes, dtype=np.int64))
-        buf = torch.zeros((len(idx), self.ld), dtype=torch.float32)
+        buf = torch.zeros((len(idx), self.ld_rows), dtype=self.dtype)
         buf[:, : self.F] = feat_data[idx]
-        self.gpu_buffer = buf.to(self.device)  # (k x ld), row i = node buffer_nodes[i]
+        self.gpu_buffer = buf.to(self.device)  # (k x ld_rows), row i = node buffer_nodes[i]
 
     def host_rows_pinned(self, node_ids: np.ndarray) -> torch.Tensor:
-        """Host gather of non-buffered rows into a pinned (n x ld) tensor (zero padding):
-        one native row-copy loop (gnn_host_gather_rows_f32, GIL released) straight into
-        the pinned buffer, so sampler worker threads stage concurrently."""
+        """Host gather of non-buffered rows into a pinned (n x ld_rows) tensor of the table's dtype
+        (zero padding): one native row-copy loop (gnn_host_gather_rows_f32 / _b16, GIL released)
+        straight into the pinned buffer, so sampler worker threads stage concurrently."""
         from . import _lib
 
         idx = np.ascontiguousarray(node_ids, dtype=np.int64)
         n = len(idx)
-        out = torch.empty((n, self.ld), dtype=torch.float32, pin_memory=torch.cuda.is_available())
+        out = torch.empty((n, self.ld_rows), dtype=self.dtype, pin_memory=torch.cuda.is_available())
         if n:
             host = self.host
-            _lib.check_sampler(_lib.sampler_lib().gnn_host_gather_rows_f32(
-                host.data_ptr(), host.stride(0), host.shape[0], idx.ctypes.data, n, self.F, out.data_ptr(), self.ld),
-                "gnn_host_gather_rows_f32")
+            L = _lib.sampler_lib()
+            fn, name = ((L.gnn_host_gather_rows_f32, "gnn_host_gather_rows_f32") if self.kind == cso.FEAT_F32 else
+                        (L.gnn_host_gather_rows_b16, "gnn_host_gather_rows_b16"))
+            _lib.check_sampler(fn(host.data_ptr(), host.stride(0), host.shape[0], idx.ctypes.data, n, self.F,
+                                  out.data_ptr(), self.ld_rows), name)
         return out
 
 
@@ -274,7 +295,8 @@ class Stager:
                     host_dev = plan.host_rows.to(dev, non_blocking=True)  # one contiguous H2D
             if self.timing is not None:
                 e1.record(st)
-                self.timing.append((e0, e1, plan.blob.nbytes if plan.blob is not None else nh * self.store.ld * 4))
+                self.timing.append((e0, e1, plan.blob.nbytes if plan.blob is not None
+                                    else nh * self.store.ld_rows * self.store.gpu_buffer.element_size()))
             if self.gate is not None:
                 # the uploads above go ahead at once (copy engine); the gathers and layer extractions
                 # below wait for the gate the step records after its layer-0 aggregation, so they run
@@ -481,11 +503,21 @@ class PeerExchange:
         dev = x0.device
         want = want_h.to(dev, non_blocking=True)
         pos = pos_h.to(dev, non_blocking=True)
-        ld = store.ld
-        send_rows = torch.empty((sum(rc), ld), dtype=torch.float32, device=dev)
+        # rows travel in the store's dtype (a 16-bit store moves half the bytes over xGMI); the
+        # final scatter widens them
+        buf = store.gpu_buffer
+        wide = buf.dtype == torch.float32
+        ld = store.ld if wide else int(buf.stride(0))
+        send_rows = torch.empty((sum(rc), ld), dtype=buf.dtype, device=dev)
         if sum(rc):
-            cso.gather_rows(store.gpu_buffer, want, send_rows, None, n=sum(rc))
-        recv_rows = torch.empty((sum(sc), ld), dtype=torch.float32, device=dev)
+            if wide:
+                cso.gather_rows(buf, want, send_rows, None, n=sum(rc))
+            else:
+                # a same-dtype copy of whole 128-byte-line rows: pairs of elements as fp32 words
+                if ld % 2:
+                    raise RuntimeError(f"PeerExchange: 16-bit buffer rows of {ld} elements are not whole words")
+                cso.gather_rows(buf.view(torch.float32), want, send_rows.view(torch.float32), None, n=sum(rc))
+        recv_rows = torch.empty((sum(sc), ld), dtype=buf.dtype, device=dev)
         self.dist.all_to_all_single(recv_rows, send_rows, output_split_sizes=sc, input_split_sizes=rc,
                                     group=self.group)
         if sum(sc):
@@ -547,7 +579,8 @@ class PeerDirect:
         self.rank = dist.get_rank(group)
         self.device = dev = store.device
         buf = store.gpu_buffer
-        self.ld = int(buf.stride(0))
+        self.ld = int(buf.stride(0))  # in the store's elements (FeatureStore.ld_rows)
+        self.kind = cso.FEAT_KIND[buf.dtype]
         self.peers = [None] * self.world  # (mapped pointer, rows, ld) per peer rank
         self.verified_rows = 0  # rows read through the mappings and checked against the feature table
         mapped = []
@@ -562,7 +595,7 @@ class PeerDirect:
                 off = ctypes.c_int64()
                 with _lib.on_device(dev):
                     _lib.check(_lib.lib().gnn_ipc_export(buf.data_ptr(), h, ctypes.byref(off)), "gnn_ipc_export")
-                info = (bytes(h), int(off.value), dev.index, int(buf.shape[0]), self.ld)
+                info = (bytes(h), int(off.value), dev.index, int(buf.shape[0]), self.ld, self.kind)
             torch.cuda.synchronize(dev)  # the buffer is final before any peer reads it
         except Exception as e:  # noqa: BLE001 — reported to every rank below
             err = f"rank {self.rank}: {e}"
@@ -574,9 +607,12 @@ class PeerDirect:
                 for j, (_, inf) in enumerate(infos):
                     if j == self.rank or inf is None:
                         continue
-                    handle, off, pdev, rows, ld = inf
+                    handle, off, pdev, rows, ld, kind = inf
+                    if kind != self.kind:
+                        raise RuntimeError(f"rank {j}'s feature store is of kind {kind}, this rank's {self.kind} "
+                                           "(0 fp32, 1 fp16, 2 bf16)")
                     if ld != self.ld:
-                        raise RuntimeError(f"rank {j}'s buffer rows are {ld} floats, this rank's {self.ld}")
+                        raise RuntimeError(f"rank {j}'s buffer rows are {ld} elements, this rank's {self.ld}")
                     ptr = ctypes.c_void_p()
                     with _lib.on_device(dev):
                         _lib.check(_lib.lib().gnn_ipc_open(handle, off, pdev if pdev != dev.index else -1,
@@ -607,12 +643,10 @@ class PeerDirect:
             slots = np.unique(np.array([0, rows // 2, rows - 1], np.int64))
             src = torch.from_numpy(slots).to(dev)
             out = torch.full((len(slots), ld), float("nan"), device=dev)
-            with _lib.on_device(dev):
-                _lib.check(_lib.lib().gnn_gather_rows_f32(ptr, ld, src.data_ptr(), out.data_ptr(), ld, None,
-                                                          len(slots), ld, _lib.stream_of(dev)), "gnn_gather_rows_f32")
+            self._gather(ptr, ld, src.data_ptr(), out.data_ptr(), ld, None, len(slots), ld, "gnn_gather_rows (verify)")
             got = out.cpu()
             nodes = torch.from_numpy(np.asarray(buffer_nodes[j], np.int64)[slots])
-            if not torch.equal(got[:, :F], feats[nodes]):
+            if not torch.equal(got[:, :F], feats[nodes].float()):
                 raise RuntimeError(f"rows read from rank {j}'s mapped buffer differ from the feature table")
             self.verified_rows += len(slots)
 
@@ -653,8 +687,21 @@ class PeerDirect:
                 pos = torch.from_numpy(np.ascontiguousarray(plan.peer_pos[j], np.int64)).to(dev, non_blocking=True)
                 src = torch.from_numpy(np.ascontiguousarray(plan.peer_src[j], np.int64)).to(dev, non_blocking=True)
             keep += [pos, src]
-            with _lib.on_device(dev):
-                _lib.check(_lib.lib().gnn_gather_rows_f32(ptr, ld, src.data_ptr(), x0.data_ptr(), x0.stride(0),
-                                                          pos.data_ptr(), n, min(ld, x0.shape[1]),
-                                                          _lib.stream_of(dev)), "gnn_gather_rows_f32 (peer)")
+            self._gather(ptr, ld, src.data_ptr(), x0.data_ptr(), x0.stride(0), pos.data_ptr(), n,
+                         min(ld, x0.shape[1]), "gnn_gather_rows (peer)")
         return tuple(keep)
+
+    def _gather(self, ptr, ld, src_idx, dst, ld_dst, dst_idx, n, F, what) -> None:
+        """Rows of a mapped peer buffer into fp32 rows on this device's current stream (16-bit
+        buffers widen on the way)."""
+        from . import _lib
+
+        dev = self.device
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            if self.kind == cso.FEAT_F32:
+                rc = L.gnn_gather_rows_f32(ptr, ld, src_idx, dst, ld_dst, dst_idx, n, F, _lib.stream_of(dev))
+            else:
+                rc = L.gnn_gather_rows_h16_f32(ptr, ld, self.kind, src_idx, dst, ld_dst, dst_idx, n, F,
+                                               _lib.stream_of(dev))
+            _lib.check(rc, what)

@@ -149,7 +149,7 @@ void gnn_ladies_free(gnn_ladies_result* r);
  * Sections are 256-byte aligned; absent sections have count 0. Element types: int32 for
  * fullrowptr / rowptr / colidx / csc_colptr / csc_rows / rows / cols / rmap, fp32 for normfact,
  * labels [batch x classes] and host_rows [n_host x ld_x0] (zero-padded rows of the feature
- * table), int64 for sampled and every placement list. Layer semantics as gnn_ladies_sample_dev
+ * table; with a 16-bit table [n_host x GNN_H_LD_HOST_ROWS] fp16 / bf16), int64 for sampled and every placement list. Layer semantics as gnn_ladies_sample_dev
  * (device-extracted layers carry rows / cols / csc_colptr / fullrowptr (= rowseg) / colseg
  * instead of the CSR pieces, int32); rmap[K]
  * (layers >= 1): rmap[sampled[i]] = i, -1 elsewhere. */
@@ -160,7 +160,11 @@ void gnn_ladies_free(gnn_ladies_result* r);
 #define GNN_BLOB_BATCH_SLOTS 16
 enum {
   GNN_H_VERSION = 0, GNN_H_LAYERS = 1, GNN_H_BYTES = 2, GNN_H_BATCH = 3, GNN_H_CLASSES = 4, GNN_H_INPUTS = 5,
-  GNN_H_WORLD = 6, GNN_H_LD_X0 = 7, GNN_H_SEED = 8, GNN_H_PINNED = 9
+  GNN_H_WORLD = 6, GNN_H_LD_X0 = 7, GNN_H_SEED = 8, GNN_H_PINNED = 9,
+  /* 16-bit feature tables (gnn_loader_set_feat_b16): the element kind of host_rows (1 fp16,
+   * 2 bf16) and its row stride in elements. Both 0 in an fp32 loader's blob: host_rows is then
+   * fp32, ld_x0 wide, as every version-1 blob before these slots were named. */
+  GNN_H_FEAT_KIND = 10, GNN_H_LD_HOST_ROWS = 11
 };
 enum {
   GNN_L_PRESENT = 0, GNN_L_ON_DEVICE = 1, GNN_L_M = 2, GNN_L_K = 3, GNN_L_NNZ = 4, GNN_L_SNUM = 5,
@@ -202,6 +206,14 @@ int gnn_loader_set_colcount(gnn_loader* ld, const gnn_colcount_api* api);
  * worker's CPU: a mix keeps both the GPU and the producers below their bound. GNN_CC_WORKERS, when
  * set, overrides. Call before the first gnn_loader_submit. */
 int gnn_loader_set_colcount_workers(gnn_loader* ld, int32_t workers);
+/* A 16-bit host feature table (kind 1: fp16, 2: bf16; the GNN_FEAT_* of gnn_spmm.h) for a loader
+ * created with feat = NULL: row stride ld_feat (elements), F features (the F of
+ * gnn_loader_create). host_rows then holds n_host x ld_rows 16-bit elements, copied unconverted
+ * with zero padding (ld_rows >= ld_x0, so the device gather may read the padded width), and the
+ * header records GNN_H_FEAT_KIND / GNN_H_LD_HOST_ROWS. `feat` is borrowed. Call before the first
+ * gnn_loader_submit. */
+int gnn_loader_set_feat_b16(gnn_loader* ld, const void* feat, int64_t ld_feat, int64_t F, int64_t ld_rows,
+                            int32_t kind);
 /* Queue one batch (node ids copied); batches come out of gnn_loader_next in submission order. */
 int gnn_loader_submit(gnn_loader* ld, uint32_t seed, const int64_t* nodes, int64_t n);
 /* Block until the oldest submitted batch is ready. On a sampling error returns its status (the
@@ -219,6 +231,10 @@ void gnn_loader_destroy(gnn_loader* ld);
  * pinned buffer that one hipMemcpyAsync then moves to the GPU. */
 int gnn_host_gather_rows_f32(const float* src, int64_t ld_src, int64_t num_src_rows, const int64_t* idx, int64_t n,
                              int64_t F, float* dst, int64_t ld_dst);
+/* The same on 2-byte elements (fp16 or bf16 tables: no conversion, so one function serves both);
+ * strides in elements. */
+int gnn_host_gather_rows_b16(const void* src, int64_t ld_src, int64_t num_src_rows, const int64_t* idx, int64_t n,
+                             int64_t F, void* dst, int64_t ld_dst);
 
 /* LADIES draw phase timers, summed over all threads since the last reset, when the process runs
  * with GNN_SAMPLER_PROFILE=1 (returns 1 otherwise): out[0..n) = seconds in scratch reset, U's

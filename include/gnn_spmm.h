@@ -178,6 +178,23 @@ int gnn_gather_rows2_f32(const float* src0, int64_t ld0, const int64_t* idx0, co
                          const float* src1, int64_t ld1, const int64_t* idx1, const int64_t* pos1, int64_t n1,
                          float* dst, int64_t ld_dst, int64_t F, void* stream);
 
+/* The same gathers from a 16-bit feature store, widening to fp32 on the way (the `.float()` of
+ * main.py:132-134): dst[dst_idx[i], 0:F] = (float)src[src_idx[i], 0:F]. `kind` names the source
+ * elements: GNN_FEAT_F16 (IEEE binary16) or GNN_FEAT_BF16; GNN_FEAT_F32 (0) is reserved for the
+ * fp32 calls above and, like any other value, refused here with a status before anything is
+ * launched. Both conversions are exact (finite values, zeros, subnormals, infinities; NaN stays
+ * NaN). Source strides in 16-bit elements, any stride >= F and any 2-byte-aligned base; rows
+ * whose stride and base are 16-byte aligned move by 16-byte loads. */
+enum { GNN_FEAT_F32 = 0, GNN_FEAT_F16 = 1, GNN_FEAT_BF16 = 2 };
+int gnn_gather_rows_h16_f32(const void* src, int64_t ld_src, int kind, const int64_t* src_idx,
+                            float* dst, int64_t ld_dst, const int64_t* dst_idx,
+                            int64_t n, int64_t F, void* stream);
+/* Two 16-bit sources of the same kind in one launch (as gnn_gather_rows2_f32); rows too wide for
+ * its one-pass kernel take gnn_gather_rows_h16_f32 per source. */
+int gnn_gather_rows2_h16_f32(const void* src0, int64_t ld0, const int64_t* idx0, const int64_t* pos0, int64_t n0,
+                             const void* src1, int64_t ld1, const int64_t* idx1, const int64_t* pos1, int64_t n1,
+                             int kind, float* dst, int64_t ld_dst, int64_t F, void* stream);
+
 /* Zero-copy variant for the non-buffered rows (replaces the pageable
  * feat_data[idx_cpu].to(device) of main.py:134): `host_src` is host memory registered with
  * gnn_host_register (pinned, device-mapped); the GPU reads the rows over PCIe, so no host

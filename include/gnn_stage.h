@@ -22,6 +22,11 @@
  *   BUFFER, LD_BUFFER             this rank's GPU feature buffer (rows of the own-buffer inputs)
  *   X0, LD_X0, F                  X0 (n_inputs x LD_X0 floats) and the row width the gathers copy
  *                                 (the padded width: buffer rows, host rows and X0 rows all hold it)
+ *   FEAT_KIND                     0 (GNN_FEAT_F32): the above, fp32. GNN_FEAT_F16 / GNN_FEAT_BF16: BUFFER
+ *                                 is a 16-bit buffer (LD_BUFFER in elements), the blob's host rows
+ *                                 are GNN_H_LD_HOST_ROWS 16-bit elements wide, and X0 is gathered by
+ *                                 gnn_gather_rows2_h16_f32. It must equal the blob's GNN_H_FEAT_KIND:
+ *                                 a mismatch is refused (by gnn_stage_plan too) before the upload
  *   INDPTR, INDICES, DEGREE, NUM_NODES, INDPTR_T, INDICES_T, ERR
  *                                 the graph on the device (sampler.DeviceGraph) for GPU-extracted
  *                                 layers, and its error flag; ERR_HOST: pinned int32 the flag is
@@ -55,7 +60,8 @@ enum {
   GNN_ST_DESC = 0, GNN_ST_HOST_BLOB = 1, GNN_ST_DEV_BLOB = 2, GNN_ST_UPLOAD = 3, GNN_ST_BUFFER = 4,
   GNN_ST_LD_BUFFER = 5, GNN_ST_X0 = 6, GNN_ST_LD_X0 = 7, GNN_ST_F = 8, GNN_ST_INDPTR = 9, GNN_ST_INDICES = 10,
   GNN_ST_DEGREE = 11, GNN_ST_NUM_NODES = 12, GNN_ST_INDPTR_T = 13, GNN_ST_INDICES_T = 14, GNN_ST_ERR = 15,
-  GNN_ST_ERR_HOST = 16, GNN_ST_GATE = 17, GNN_ST_CSC_FROM = 18, GNN_ST_ARENA = 19, GNN_ST_ARENA_BYTES = 20
+  GNN_ST_ERR_HOST = 16, GNN_ST_GATE = 17, GNN_ST_CSC_FROM = 18, GNN_ST_ARENA = 19, GNN_ST_ARENA_BYTES = 20,
+  GNN_ST_FEAT_KIND = 21
 };
 
 enum { GNN_SO_ROWPTR = 0, GNN_SO_COL = 1, GNN_SO_VAL = 2, GNN_SO_ROWS_T = 3, GNN_SO_VAL_T = 4, GNN_SO_WORKSPACE = 5 };
