@@ -159,8 +159,44 @@ struct WorkMap {
   }
 };
 
+// Element kind of X (GNN_FEAT_*). fp32 rows are loaded as the V the FMAs take. 16-bit rows (VW 4
+// only) are loaded 4 elements at a time as two 32-bit words (8 bytes, global_load_dwordx2), kept as
+// loaded until the FMAs and widened there in registers: bf16 is the upper half of the fp32 pattern
+// (a shift / a mask of the word), fp16 the hardware convert of each half (fp16 denormals are on in
+// gfx9 code objects), both exact — so the fmaf chain sees the values the fp32 kernel reads from the
+// widened copy of X and gives the same bits. Two zero words widen to the fp32 zero vector the
+// skipped slots use.
+typedef unsigned int xw2 __attribute__((ext_vector_type(2)));
+template <int XK, int VW> struct XLoad {
+  using E = float;
+  using T = typename Vec<VW>::T;
+  static __device__ __forceinline__ T widen(T x) { return x; }
+};
+template <int VW> struct XLoad<GNN_FEAT_F16, VW> {
+  static_assert(VW == 4, "16-bit X rows are read 4 elements per load");
+  using E = unsigned short;
+  using T = xw2;
+  static __device__ __forceinline__ float half_of(unsigned w, int hi) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)(hi ? w >> 16 : w & 0xffffu));
+  }
+  static __device__ __forceinline__ f4 widen(xw2 x) {
+    return f4{half_of(x.x, 0), half_of(x.x, 1), half_of(x.y, 0), half_of(x.y, 1)};
+  }
+};
+template <int VW> struct XLoad<GNN_FEAT_BF16, VW> {
+  static_assert(VW == 4, "16-bit X rows are read 4 elements per load");
+  using E = unsigned short;
+  using T = xw2;
+  static __device__ __forceinline__ f4 widen(xw2 x) {
+    return f4{__uint_as_float(x.x << 16), __uint_as_float(x.x & 0xffff0000u), __uint_as_float(x.y << 16),
+              __uint_as_float(x.y & 0xffff0000u)};
+  }
+};
+
 // One column chunk per lane: held to 8 waves per SIMD (<= 64 VGPRs; the slot-skip branches
 // below otherwise take 66); wider instantiations keep the compiler's choice (no spills).
+// The body is spmm_unit_body.inc, shared as text with the 16-bit kernel below (a shared device
+// function, inlined, changed the fp32 kernel's code: 50 -> 64 VGPRs for <4, 16, 1, 4, false>).
 template <int VW, int G, int NJ, int U, bool RES>
 __global__ __launch_bounds__(256, (NJ == 1 && U <= 4) ? 8 : 1) void spmm_unit_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
@@ -169,161 +205,26 @@ __global__ __launch_bounds__(256, (NJ == 1 && U <= 4) ? 8 : 1) void spmm_unit_ke
     float* __restrict__ Y, int64_t ldy,
     float* __restrict__ slab, int64_t ldslab, int F,
     const float* __restrict__ R, int64_t ldr, const int* __restrict__ rmap, WorkMap wm) {
-  using V = typename Vec<VW>::T;
-  constexpr int P = 64 / G;            // nonzeros taken side by side per step
-  constexpr int COVER = VW * G * NJ;   // columns covered by one column tile
-  const int lane = threadIdx.x & 63;
-  int ub, tile;
-  if (!wm.locate(blockIdx.x, ub, tile)) return;
-  const int u = ub * 4 + (threadIdx.x >> 6);  // wave-uniform; no block barriers below
-  const int sub = lane / G;
-  const int c0 = tile * COVER + (lane % G) * VW;
-  if (u >= nunits) {  // row unit: the empty rows among ROW_UNIT consecutive rows
-    const int r0 = (u - nunits) * ROW_UNIT;
-    if (r0 >= M) return;
-    const int rl = r0 + lane;
-    unsigned long long em = __ballot(rl < M && rowptr[rl] == rowptr[rl + 1]);
-    while (em) {
-      const int r = r0 + __builtin_ctzll(em);
-      em &= em - 1;
-      const float* res = nullptr;
-      if constexpr (RES) {
-        const int q = rmap[r];
-        if (q >= 0) res = R + (int64_t)q * ldr;
-      }
-      float* dst = Y + (int64_t)r * ldy;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int cc = c0 + j * G * VW;
-        if ((j % P) == sub && cc < F) {
-          V a = vzero<VW>();
-          if constexpr (RES) {
-            if (res) a = *reinterpret_cast<const V*>(res + cc);
-          }
-          *reinterpret_cast<V*>(dst + cc) = a;
-        }
-      }
-    }
-    return;
-  }
+  constexpr int XK = GNN_FEAT_F32;
+#include "spmm_unit_body.inc"
+}
 
-  const int ustart = u * S;  // host guarantees nunits * S fits in int
-  const int uend = min(ustart + S, nnz);
-
-  // Row ownership: a row of at most S nonzeros belongs wholly to the unit holding its first
-  // nonzero (it may run past uend, by < S); only longer rows are cut at unit boundaries.
-  // rlo = the row containing position ustart (or the first row starting at/after it).
-  const int rlo = wave_first_true(0, M, lane, [&](int r) {
-    return rowptr[r + 1] > ustart || rowptr[r] >= ustart;
-  });
-  // (rows starting at or after uend belong to later units; trailing empty rows start at nnz)
-  const int rhi = wave_first_true(rlo, M, lane, [&](int r) { return rowptr[r] >= uend; });
-
-  for (int r = rlo; r < rhi; ++r) {
-    const int rb = rowptr[r];
-    const int re = rowptr[r + 1];
-    if (rb == re) {  // empty: a row unit stores it; skip the whole run of empty rows at rb
-      r = wave_first_true(r + 1, rhi, lane, [&](int q) { return rowptr[q + 1] > rb; }) - 1;
-      continue;
-    }
-    const bool cut = re - rb > S;  // wave-uniform
-    if (rb < ustart && !cut) continue;  // short row owned by an earlier unit
-    const int b = max(rb, ustart);
-    const int e = cut ? min(re, uend) : re;
-    V acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = vzero<VW>();
-
-    for (int base = b; base < e; base += 64) {
-      const int n = min(64, e - base);
-      int mc = 0;
-      float mv = 0.0f;
-      if (lane < n) {
-        mc = col[base + lane];
-        mv = val[base + lane];
-      }
-      const int last_c = __shfl(mc, n - 1);
-      for (int k = 0; k < n; k += P * U) {
-        V xs[U][NJ];
-        float vs[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-          const int idx = k + t * P + sub;
-          int c;
-          float v;
-          // idx may run past the chunk (and past lane 63, where lane selects wrap):
-          // such padded slots get v = 0 and re-read a row already in flight.
-          if constexpr (P == 1) {
-            c = readlane_i(mc, idx & 63);  // idx is wave-uniform: scalar row address
-            v = readlane_f(mv, idx & 63);
-          } else {
-            c = __shfl(mc, idx & 63);
-            v = __shfl(mv, idx & 63);
-          }
-          if (idx >= n) {
-            c = last_c;
-            v = 0.0f;
-          }
-          vs[t] = v;
-          const float* xr = X + (int64_t)c * ldx;
-          // a slot past the row end for every lane group (the row's last, partly empty round:
-          // 6-7 % of the slots on the Reddit layers) issues no load; its FMA adds 0 * 0, as the
-          // loaded-and-masked slot added 0 * x: bit-identical (A/B: layer-0 forward -1 %)
-          if (k + t * P >= n) {  // wave-uniform
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) xs[t][j] = vzero<VW>();
-            continue;
-          }
-          // Columns past F load the row's last vector instead (same cache lines, no
-          // branch, no extra HBM bytes); those accumulator slots are never stored.
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            const int cc = min(c0 + j * G * VW, F - VW);
-            xs[t][j] = *reinterpret_cast<const V*>(xr + cc);
-          }
-        }
-        // keep all U * NJ row loads ahead of the FMAs (the scheduler otherwise interleaves
-        // them to raise occupancy, leaving fewer loads in flight per wave)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[j] = vfma(vs[t], xs[t][j], acc[j]);
-        }
-      }
-    }
-
-    if constexpr (P > 1) {
-#pragma unroll
-      for (int m = G; m < 64; m <<= 1) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[j] += shfl_xor_v(acc[j], m);
-      }
-    }
-
-    float* dst;
-    const float* res = nullptr;  // residual row added to a complete output row
-    if (!cut) {
-      dst = Y + (int64_t)r * ldy;
-      if constexpr (RES) {
-        const int q = rmap[r];
-        if (q >= 0) res = R + (int64_t)q * ldr;
-      }
-    } else {
-      dst = slab + ((int64_t)u * 2 + (rb < ustart ? 0 : 1)) * ldslab;
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int cc = c0 + j * G * VW;
-      if ((j % P) == sub && cc < F) {
-        V a = acc[j];
-        if constexpr (RES) {
-          if (res) a += *reinterpret_cast<const V*>(res + cc);
-        }
-        *reinterpret_cast<V*>(dst + cc) = a;
-      }
-    }
-  }
+// The same walk over 16-bit X rows (KIND = GNN_FEAT_F16 / GNN_FEAT_BF16; ldx in elements), VW 4 and
+// no residual: layer 0 aggregating straight from a 16-bit feature store's rows. Launched with the
+// geometry of the fp32 call (G, NJ, tiles, S, WorkMap), it is bit-identical to it on widened X.
+template <int KIND, int G, int NJ, int U>
+__global__ __launch_bounds__(256, (NJ == 1 && U <= 4) ? 8 : 1) void spmm_unit16_kernel(
+    const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
+    int M, int nnz, int S, int nunits,
+    const unsigned short* __restrict__ X, int64_t ldx,
+    float* __restrict__ Y, int64_t ldy,
+    float* __restrict__ slab, int64_t ldslab, int F, WorkMap wm) {
+  constexpr int XK = KIND, VW = 4;
+  constexpr bool RES = false;
+  const float* const R = nullptr;  // named by the body's discarded residual branches
+  const int64_t ldr = 0;
+  const int* const rmap = nullptr;
+#include "spmm_unit_body.inc"
 }
 
 // Adds the unit pieces of every cut row (> S nonzeros), in unit order. A workgroup covers
@@ -402,92 +303,27 @@ __global__ __launch_bounds__(256) void spmm_combine_kernel(
 // the oracle); WPR > 1: WPR such chains added in order (deterministic). Empty rows store zeros
 // (or the residual row).
 // ---------------------------------------------------------------------------------
+
 template <int VW, int NJ, int U, int WPR, bool RES>
 __global__ __launch_bounds__(64 * WPR) void spmm_row_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val, int M,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int F, int slices,
     const float* __restrict__ R, int64_t ldr, const int* __restrict__ rmap) {
-  using V = typename Vec<VW>::T;
-  constexpr int COVER = 64 * VW * NJ;
-  __shared__ V part[WPR > 1 ? WPR - 1 : 1][NJ][64];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int r = (int)(blockIdx.x / (unsigned)slices);
-  const int s = (int)(blockIdx.x - (unsigned)r * (unsigned)slices);
-  if (r >= M) return;
-  const int c0 = s * COVER + lane * VW;
-  int q = -1;
-  if constexpr (RES) q = rmap[r];  // issued early: its latency overlaps the walk
-  const int rb = rowptr[r];
-  const int re = rowptr[r + 1];
-  const int per = (re - rb + WPR - 1) / WPR;
-  const int b = rb + w * per;
-  const int e = min(re, b + per);
-  V acc[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) acc[j] = vzero<VW>();
-  for (int base = b; base < e; base += 64) {
-    const int n = min(64, e - base);
-    int mc = 0;
-    float mv = 0.0f;
-    if (lane < n) {
-      mc = col[base + lane];
-      mv = val[base + lane];
-    }
-    for (int k = 0; k < n; k += U) {
-      V xs[U][NJ];
-      float vs[U];
-#pragma unroll
-      for (int t = 0; t < U; ++t) {
-        const int idx = k + t;  // wave-uniform
-        if (idx >= n) {        // past the chunk: no load, the FMA adds 0 * 0
-          vs[t] = 0.0f;
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) xs[t][j] = vzero<VW>();
-          continue;
-        }
-        const int c = readlane_i(mc, idx);  // scalar row address
-        vs[t] = readlane_f(mv, idx);
-        const float* xr = X + (int64_t)c * ldx;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int cc = min(c0 + j * 64 * VW, F - VW);  // past F: the row's last vector (unstored)
-          xs[t][j] = *reinterpret_cast<const V*>(xr + cc);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);  // all U * NJ row loads ahead of the FMAs
-#pragma unroll
-      for (int t = 0; t < U; ++t) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[j] = vfma(vs[t], xs[t][j], acc[j]);
-      }
-    }
-  }
-  if constexpr (WPR > 1) {
-    if (w > 0) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) part[w - 1][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (w > 0) return;
-#pragma unroll
-    for (int p = 0; p < WPR - 1; ++p) {  // wave order: deterministic
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[j] += part[p][j][lane];
-    }
-  }
-  float* dst = Y + (int64_t)r * ldy;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int cc = c0 + j * 64 * VW;
-    if (cc < F) {
-      V a = acc[j];
-      if constexpr (RES) {
-        if (q >= 0) a += *reinterpret_cast<const V*>(R + (int64_t)q * ldr + cc);
-      }
-      *reinterpret_cast<V*>(dst + cc) = a;
-    }
-  }
+  constexpr int XK = GNN_FEAT_F32;
+#include "spmm_row_body.inc"
+}
+
+// 16-bit X rows (see spmm_unit16_kernel): VW 4, no residual.
+template <int KIND, int NJ, int U, int WPR>
+__global__ __launch_bounds__(64 * WPR) void spmm_row16_kernel(
+    const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val, int M,
+    const unsigned short* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int F, int slices) {
+  constexpr int XK = KIND, VW = 4;
+  constexpr bool RES = false;
+  const float* const R = nullptr;
+  const int64_t ldr = 0;
+  const int* const rmap = nullptr;
+#include "spmm_row_body.inc"
 }
 
 // ---------------------------------------------------------------------------------
@@ -1456,10 +1292,15 @@ int64_t default_unit(int64_t M, int64_t nnz, int64_t F) {
   return s;
 }
 
+// x16: X rows are 16-bit (gnn_spmm_csr_h16_f32). The call has checked that 4 elements per load
+// fit, and everything below is then what the fp32 call picks at VW 4 for this (M, K, nnz, F): the
+// summation order of an output depends on G, the unit size and the row kernel's WPR, so equal
+// geometry makes the two calls bit-identical on equal values. The L2 tile rule stays in fp32
+// columns: a tile's slice of 16-bit X is half the bytes.
 SpmmCfg make_cfg(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, int64_t ldy, const void* X,
-                 const void* Y, int64_t unit) {
+                 const void* Y, int64_t unit, bool x16 = false) {
   SpmmCfg c{};
-  c.vw = pick_vw(F, ldx, ldy, X, Y);
+  c.vw = x16 ? 4 : pick_vw(F, ldx, ldy, X, Y);
   double best = -1.0;
   const int gs[3] = {64, 32, 16};
   for (int gi = 0; gi < 3; ++gi) {
@@ -1512,7 +1353,7 @@ SpmmCfg make_cfg(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, int6
     const char* en = getenv("GNN_SPMM_NJ");
     const int nj = en ? atoi(en) : 1;
     const char* ev = getenv("GNN_SPMM_VW");
-    if (ev && atoi(ev) >= 1 && atoi(ev) < c.vw && (atoi(ev) & (atoi(ev) - 1)) == 0) c.vw = atoi(ev);
+    if (!x16 && ev && atoi(ev) >= 1 && atoi(ev) < c.vw && (atoi(ev) & (atoi(ev) - 1)) == 0) c.vw = atoi(ev);
     if ((g == 8 || g == 16 || g == 32 || g == 64) && nj >= 1 && nj <= 8) {
       c.g = g;
       c.nj = nj;
@@ -1613,6 +1454,57 @@ RowFn select_row(const SpmmCfg& c, bool res) {
   if (c.rnj != 1) return nullptr;
   if (c.vw == 2) return row_by_wpr<2, 1, 16>(c.wpr, res);
   return row_by_wpr<1, 1, 16>(c.wpr, res);
+}
+
+// 16-bit X: VW 4, no residual, G 64 / 32 / 16 (what make_cfg picks without the GNN_SPMM_G override).
+using Main16Fn = void (*)(const int*, const int*, const float*, int, int, int, int, const unsigned short*, int64_t,
+                          float*, int64_t, float*, int64_t, int, WorkMap);
+
+template <int KIND, int G>
+Main16Fn main16_by_nj(int nj) {
+  switch (nj) {
+    case 1: return &spmm_unit16_kernel<KIND, G, 1, pick_u(1)>;
+    case 2: return &spmm_unit16_kernel<KIND, G, 2, pick_u(2)>;
+    case 3: return &spmm_unit16_kernel<KIND, G, 3, pick_u(3)>;
+    case 4: return &spmm_unit16_kernel<KIND, G, 4, pick_u(4)>;
+    case 5: return &spmm_unit16_kernel<KIND, G, 5, pick_u(5)>;
+    case 6: return &spmm_unit16_kernel<KIND, G, 6, pick_u(6)>;
+    case 7: return &spmm_unit16_kernel<KIND, G, 7, pick_u(7)>;
+    case 8: return &spmm_unit16_kernel<KIND, G, 8, pick_u(8)>;
+    default: return nullptr;
+  }
+}
+
+template <int KIND>
+Main16Fn select_main16(const SpmmCfg& c) {
+  if (c.u16 && c.g == 64 && c.nj == 1) return &spmm_unit16_kernel<KIND, 64, 1, 16>;
+  switch (c.g) {
+    case 64: return main16_by_nj<KIND, 64>(c.nj);
+    case 32: return main16_by_nj<KIND, 32>(c.nj);
+    case 16: return main16_by_nj<KIND, 16>(c.nj);
+    default: return nullptr;
+  }
+}
+
+using Row16Fn = void (*)(const int*, const int*, const float*, int, const unsigned short*, int64_t, float*, int64_t,
+                         int, int);
+
+template <int KIND, int NJ, int U>
+Row16Fn row16_by_wpr(int wpr) {
+  switch (wpr) {
+    case 1: return &spmm_row16_kernel<KIND, NJ, U, 1>;
+    case 2: return &spmm_row16_kernel<KIND, NJ, U, 2>;
+    case 4: return &spmm_row16_kernel<KIND, NJ, U, 4>;
+    case 8: return &spmm_row16_kernel<KIND, NJ, U, 8>;
+    default: return nullptr;
+  }
+}
+
+template <int KIND>
+Row16Fn select_row16(const SpmmCfg& c) {
+  if (c.rnj == 4) return row16_by_wpr<KIND, 4, 4>(c.wpr);
+  if (c.rnj == 2) return row16_by_wpr<KIND, 2, 8>(c.wpr);
+  return row16_by_wpr<KIND, 1, 16>(c.wpr);
 }
 
 // The main kernel's name as rocprofv3 lists it (bench.py's per-kernel roofline).
@@ -1722,6 +1614,21 @@ int gnn_spmm_config(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, i
   return 0;
 }
 
+int gnn_spmm_h16_config(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, int64_t ldy, const void* X,
+                        const void* Y, int64_t unit_nnz, int32_t out[8]) {
+  GNN_REQUIRE(out != nullptr, "gnn_spmm_h16_config: out is NULL");
+  const SpmmCfg c = make_cfg(M, K, nnz, F, ldx, ldy, X, Y, unit_nnz, true);
+  out[0] = c.vw;
+  out[1] = c.g;
+  out[2] = c.nj;
+  out[3] = c.tiles;
+  out[4] = (int32_t)c.unit;
+  out[5] = (int32_t)c.nunits;
+  out[6] = c.wpr;
+  out[7] = 4;  // 16-bit elements per load
+  return 0;
+}
+
 void gnn_spmm_set_timing_events(void* start, void* stop) {
   g_ev_start = (hipEvent_t)start;
   g_ev_stop = (hipEvent_t)stop;
@@ -1803,6 +1710,72 @@ int gnn_spmm_csr_f32_ex(const int32_t* rowptr, const int32_t* col, const float* 
     if (c.vw == 4) combine(spmm_combine_kernel<4, COMBINE_LOADS>);
     else if (c.vw == 2) combine(spmm_combine_kernel<2, COMBINE_LOADS>);
     else combine(spmm_combine_kernel<1, COMBINE_LOADS>);
+    GNN_LAUNCHED("spmm_combine_kernel");
+  }
+  return 0;
+}
+
+int gnn_spmm_csr_h16_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t M, int64_t K,
+                         int64_t nnz, const void* X, int64_t ldx, int kind, float* Y, int64_t ldy, int64_t F,
+                         void* workspace, size_t workspace_bytes, int64_t unit_nnz, void* stream) {
+  hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
+  g_ev_start = g_ev_stop = nullptr;
+  GNN_REQUIRE(kind == GNN_FEAT_F16 || kind == GNN_FEAT_BF16,
+              "gnn_spmm_csr_h16_f32: kind %d is neither GNN_FEAT_F16 (1) nor GNN_FEAT_BF16 (2)", kind);
+  GNN_REQUIRE(M >= 0 && K >= 0 && nnz >= 0 && F >= 0, "gnn_spmm_csr_h16_f32: negative size");
+  GNN_REQUIRE(M < INT_MAX && K < INT_MAX && nnz < INT_MAX, "gnn_spmm_csr_h16_f32: M, K, nnz must be < 2^31");
+  GNN_REQUIRE(F <= ldx, "gnn_spmm_csr_h16_f32: F (%lld) > ldx (%lld)", (long long)F, (long long)ldx);
+  GNN_REQUIRE(F <= ldy, "gnn_spmm_csr_h16_f32: F (%lld) > ldy (%lld)", (long long)F, (long long)ldy);
+  // 4 elements per load and no scalar form: callers whose rows do not fit widen first
+  GNN_REQUIRE(F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0,
+              "gnn_spmm_csr_h16_f32: F (%lld), ldx (%lld) and ldy (%lld) must be multiples of 4", (long long)F,
+              (long long)ldx, (long long)ldy);
+  GNN_REQUIRE((uintptr_t)X % 8 == 0, "gnn_spmm_csr_h16_f32: X not 8-byte aligned");
+  GNN_REQUIRE((uintptr_t)Y % 16 == 0, "gnn_spmm_csr_h16_f32: Y not 16-byte aligned");
+  if (M == 0 || F == 0) return 0;
+  GNN_REQUIRE(rowptr && Y, "gnn_spmm_csr_h16_f32: NULL rowptr/Y");
+  GNN_REQUIRE(nnz == 0 || (col && val && X), "gnn_spmm_csr_h16_f32: NULL col/val/X");
+  const SpmmCfg c = make_cfg(M, K, nnz, F, ldx, ldy, X, Y, unit_nnz, true);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* X16 = (const unsigned short*)X;
+  if (c.wpr) {
+    Row16Fn fn = kind == GNN_FEAT_F16 ? select_row16<GNN_FEAT_F16>(c) : select_row16<GNN_FEAT_BF16>(c);
+    GNN_REQUIRE(fn != nullptr, "gnn_spmm_csr_h16_f32: no row kernel for nj=%d wpr=%d", c.rnj, c.wpr);
+    if (ev0 || ev1)
+      hipExtLaunchKernelGGL(fn, dim3((unsigned)(M * c.slices)), dim3(64 * c.wpr), 0, st, ev0, ev1, 0, rowptr, col, val,
+                            (int)M, X16, ldx, Y, ldy, (int)F, c.slices);
+    else
+      hipLaunchKernelGGL(fn, dim3((unsigned)(M * c.slices)), dim3(64 * c.wpr), 0, st, rowptr, col, val, (int)M, X16,
+                         ldx, Y, ldy, (int)F, c.slices);
+    GNN_LAUNCHED("spmm_row16_kernel");
+    return 0;
+  }
+  GNN_REQUIRE(c.nunits * c.unit < (int64_t)INT_MAX + c.unit, "gnn_spmm_csr_h16_f32: unit overflow");
+  GNN_REQUIRE(c.nunits <= (int64_t)INT_MAX / 2, "gnn_spmm_csr_h16_f32: too many units");
+  const size_t need = align_up((size_t)c.nunits * 2 * (size_t)c.ldslab * sizeof(float), 256);
+  const bool any_split = c.nunits > 1;
+  GNN_REQUIRE(!any_split || (workspace && workspace_bytes >= need),
+              "gnn_spmm_csr_h16_f32: workspace too small (%zu < %zu)", workspace_bytes, need);
+  GNN_REQUIRE((uintptr_t)workspace % 16 == 0, "gnn_spmm_csr_h16_f32: workspace not 16-byte aligned");
+  Main16Fn fn = kind == GNN_FEAT_F16 ? select_main16<GNN_FEAT_F16>(c) : select_main16<GNN_FEAT_BF16>(c);
+  GNN_REQUIRE(fn != nullptr, "gnn_spmm_csr_h16_f32: no kernel for g=%d nj=%d", c.g, c.nj);
+  float* slab = (float*)workspace;
+  GNN_REQUIRE(ceil_div(c.nunits + ceil_div(M, (int64_t)ROW_UNIT), 4) * c.tiles < (int64_t)INT_MAX - 8,
+              "gnn_spmm_csr_h16_f32: grid too large");
+  const WorkMap wm = work_map(c, M);
+  const dim3 grid((unsigned)(wm.xcd_chunk ? 8 * (int64_t)wm.xcd_chunk : wm.items));
+  if (ev0 || ev1)
+    hipExtLaunchKernelGGL(fn, grid, dim3(256), 0, st, ev0, ev1, 0, rowptr, col, val, (int)M, (int)nnz, (int)c.unit,
+                          (int)c.nunits, X16, ldx, Y, ldy, slab, c.ldslab, (int)F, wm);
+  else
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, rowptr, col, val, (int)M, (int)nnz, (int)c.unit, (int)c.nunits, X16,
+                       ldx, Y, ldy, slab, c.ldslab, (int)F, wm);
+  GNN_LAUNCHED("spmm_unit16_kernel");
+  if (any_split) {  // the fp32 call's combine: the slab and Y are fp32 either way
+    int crows = combine_rows(M);
+    if (const char* e = getenv("GNN_SPMM_CROWS")) crows = std::min(64, std::max(1, atoi(e)));  // A/B
+    spmm_combine_kernel<4, COMBINE_LOADS><<<dim3((unsigned)ceil_div(M, (int64_t)crows)), dim3(256), 0, st>>>(
+        rowptr, (int)M, (int)c.unit, slab, c.ldslab, Y, ldy, (int)F, nullptr, 0, nullptr, crows);
     GNN_LAUNCHED("spmm_combine_kernel");
   }
   return 0;

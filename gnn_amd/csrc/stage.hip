@@ -7,7 +7,8 @@
 // runs slow. Here the training thread makes two calls (plan, stage) and this file issues, on the
 // staging stream, the library calls the Python path made, with the same arguments:
 //   blob upload -> [gate] -> X0 gather (own-buffer + host rows, gnn_gather_rows2_f32; from a
-//   16-bit feature store, GNN_ST_FEAT_KIND, the widening gnn_gather_rows2_h16_f32) ->
+//   16-bit feature store, GNN_ST_FEAT_KIND, the widening gnn_gather_rows2_h16_f32, or with a
+//   16-bit X0, GNN_ST_X0_KIND, the fp32 gather over the rows as whole words: a copy) ->
 //   per layer: gnn_ladies_extract_f32 (GPU-extracted) | gnn_build_operand_sorted_f32 (+ _t on the
 //   blob's CSC) -> the extraction error flag into pinned host memory.
 // No kernels of its own; nothing allocated (the caller's arena holds every output and the
@@ -82,6 +83,12 @@ size_t plan(const int64_t* a, int64_t* out) {
   if ((kind != GNN_FEAT_F32 && kind != GNN_FEAT_F16 && kind != GNN_FEAT_BF16) || kind != d[GNN_H_FEAT_KIND]) {
     gnn::fail(GNN_EINVAL, "gnn_stage: feature kind %lld does not match the blob's %lld (0 fp32, 1 fp16, 2 bf16)",
               (long long)kind, (long long)d[GNN_H_FEAT_KIND]);
+    return 0;
+  }
+  // a 16-bit X0 keeps the store's elements: its kind is the store's, or 0 (fp32, widened into)
+  if (a[GNN_ST_X0_KIND] != GNN_FEAT_F32 && a[GNN_ST_X0_KIND] != kind) {
+    gnn::fail(GNN_EINVAL, "gnn_stage: X0 kind %lld is neither 0 (fp32) nor the feature kind %lld",
+              (long long)a[GNN_ST_X0_KIND], (long long)kind);
     return 0;
   }
   BlobView b{d, AP<const char>(a, GNN_ST_HOST_BLOB), nullptr, (int)d[GNN_H_LAYERS]};
@@ -167,14 +174,30 @@ int gnn_stage_batch_f32(const int64_t* a, void* stream) {
   const int64_t n_own = b.count(B + GNN_B_OWN_POS), nh = b.count(B + GNN_B_HOST_POS);
   const int64_t ld_x0 = a[GNN_ST_LD_X0];
   float* x0 = AP<float>(a, GNN_ST_X0);
-  GNN_REQUIRE(x0 && ld_x0 == d[GNN_H_LD_X0], "gnn_stage_batch_f32: X0 NULL or its stride %lld != the blob's %lld",
-              (long long)ld_x0, (long long)d[GNN_H_LD_X0]);
   const int kind = (int)a[GNN_ST_FEAT_KIND];  // equals the blob's (plan)
+  const bool x16 = a[GNN_ST_X0_KIND] != GNN_FEAT_F32;  // then equals kind (plan): X0 keeps the 16-bit rows
+  // (an fp32 X0 has the blob's stride in floats; a 16-bit X0 its host rows' stride in elements)
+  const int64_t ld_blob = x16 ? d[GNN_H_LD_HOST_ROWS] : d[GNN_H_LD_X0];
+  GNN_REQUIRE(x0 && ld_x0 == ld_blob, "gnn_stage_batch_f32: X0 NULL or its stride %lld != the blob's %lld",
+              (long long)ld_x0, (long long)ld_blob);
   const int64_t ld_host = kind == GNN_FEAT_F32 ? ld_x0 : d[GNN_H_LD_HOST_ROWS];
   GNN_REQUIRE(nh == 0 || b.count(B + GNN_B_HOST_ROWS) == nh * ld_host,
               "gnn_stage_batch_f32: the blob holds no host rows (zero-copy batches stage through Python)");
   GNN_REQUIRE(n_own == 0 || a[GNN_ST_BUFFER], "gnn_stage_batch_f32: NULL feature buffer");
-  if (kind == GNN_FEAT_F32)
+  if (x16) {
+    // rows copied as they are: pairs of elements as fp32 words (whole-word rows and an even width;
+    // the pad columns come out zero because the sources' are)
+    GNN_REQUIRE(ld_x0 % 2 == 0 && ld_host % 2 == 0 && a[GNN_ST_LD_BUFFER] % 2 == 0 && a[GNN_ST_F] % 2 == 0 &&
+                    (uintptr_t)x0 % 4 == 0 && a[GNN_ST_BUFFER] % 4 == 0,
+                "gnn_stage_batch_f32: 16-bit X0, buffer and host rows must be whole 4-byte words (strides %lld, "
+                "%lld, %lld, width %lld)",
+                (long long)ld_x0, (long long)a[GNN_ST_LD_BUFFER], (long long)ld_host, (long long)a[GNN_ST_F]);
+    GNN_STAGE_TRY(gnn_gather_rows2_f32(AP<const float>(a, GNN_ST_BUFFER), a[GNN_ST_LD_BUFFER] / 2,
+                                       b.dv<const int64_t>(B + GNN_B_OWN_SRC), b.dv<const int64_t>(B + GNN_B_OWN_POS),
+                                       n_own, nh ? b.dv<const float>(B + GNN_B_HOST_ROWS) : x0, ld_host / 2, nullptr,
+                                       b.dv<const int64_t>(B + GNN_B_HOST_POS), nh, x0, ld_x0 / 2, a[GNN_ST_F] / 2,
+                                       stream));
+  } else if (kind == GNN_FEAT_F32)
     GNN_STAGE_TRY(gnn_gather_rows2_f32(AP<const float>(a, GNN_ST_BUFFER), a[GNN_ST_LD_BUFFER],
                                  b.dv<const int64_t>(B + GNN_B_OWN_SRC), b.dv<const int64_t>(B + GNN_B_OWN_POS), n_own,
                                  nh ? b.dv<const float>(B + GNN_B_HOST_ROWS) : x0, ld_x0, nullptr,

@@ -17,7 +17,8 @@
 //
 // Sequence (L layers, bottom-up index l; layer 0's input is the features, so it has no input
 // gradient):
-//   forward  l = 0..L-1:  feat = A_l·X (gnn_spmm_csr_f32);  [SAGE] xs = X[sampled] (row gather)
+//   forward  l = 0..L-1:  feat = A_l·X (gnn_spmm_csr_f32; layer 0 over 16-bit X0 rows, GNN_SL_XKIND:
+//                         gnn_spmm_csr_h16_f32);  [SAGE] xs = X[sampled] (row gather; widening there)
 //                         [hB,] hW = [xs, feat]·[W_B, W_W]ᵀ  (one batched split3 launch or rocBLAS)
 //                         Y_l = sage_norm(hB + b_B, hW + b_W)  (ELU, row standardise, scale/offset, dropout)
 //   head:                 loss, z = BCE or CE(linear(dropout(normalize(Y_{L-1}))))
@@ -238,6 +239,10 @@ struct LayerBufs {
   int64_t M, K, nnz, F, Fk, ldx, ldo, N, D;
   bool xs_gathered;  // false: x[sampled] is read in place by the split3 GEMMs (row-indexed X)
   const float* X;
+  // layer 0 over a 16-bit X0 (GNN_SL_XKIND = GNN_FEAT_F16 / GNN_FEAT_BF16): X is NULL, X16 the rows
+  // (ldx in elements); the aggregation reads them as they are and x[sampled] is widened into xs
+  int xk;
+  const void* X16;
   float *feat, *xs, *hB, *hW, *Y, *mean, *rstd;
   float *dY, *dhB, *dhW, *dxs, *dfeat;
   void *ws_fwd, *ws_bwd, *ws_norm, *ws_gemm_f, *ws_gemm_f2, *ws_gemm_dx, *ws_gemm_dw;
@@ -285,8 +290,15 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
     b.nnz = L(d, l, GNN_SL_NNZ);
     b.N = N;
     b.D = n * N;
+    const int64_t xk = L(d, l, GNN_SL_XKIND);
+    GNN_REQUIRE(xk == GNN_FEAT_F32 || (l == 0 && (xk == GNN_FEAT_F16 || xk == GNN_FEAT_BF16)),
+                "gnn_train_step: layer %d input kind %lld (0: fp32; 1 fp16 / 2 bf16 on layer 0 only)", l,
+                (long long)xk);
+    b.xk = (int)xk;
+    b.X16 = nullptr;
     if (l == 0) {
-      b.X = HP<const float>(d, GNN_SH_X0);
+      b.X = xk ? nullptr : HP<const float>(d, GNN_SH_X0);
+      b.X16 = xk ? HP<const void>(d, GNN_SH_X0) : nullptr;
       b.ldx = d[GNN_SH_LDX0];
       b.F = d[GNN_SH_F0];
     } else {
@@ -305,6 +317,17 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
         b.ldx >= b.F + (4 - b.F % 4))
       b.Fk = b.F + (4 - b.F % 4);
     b.ldo = (b.Fk != b.F && b.ldx <= 2 * b.Fk) ? b.ldx : b.Fk;
+    if (xk) {
+      // 16-bit rows: 4 elements per load and no narrower form (gnn_spmm_csr_h16_f32), so the padded
+      // width must fit the row; the output takes the stride an fp32 X0 of this store has (whole
+      // 128-byte lines), so the workspace is that of the widened step
+      GNN_REQUIRE(b.ldx % 4 == 0 && ((uintptr_t)b.X16 % 8 == 0 || measuring),
+                  "gnn_train_step: 16-bit x0 needs 8-byte aligned rows (ldx %lld)", (long long)b.ldx);
+      b.Fk = (int64_t)align_up((size_t)b.F, 4);
+      GNN_REQUIRE(b.Fk <= b.ldx, "gnn_train_step: 16-bit x0 rows of %lld elements have no room for %lld columns",
+                  (long long)b.ldx, (long long)b.Fk);
+      b.ldo = (int64_t)align_up((size_t)b.Fk, 32);
+    }
     b.b_fwd = gnn_spmm_workspace_bytes(b.M, b.nnz, b.Fk, 0);
     b.b_gemm_f = gemm_ws(b.M, N, b.F, n);
   }
@@ -444,12 +467,32 @@ struct Run {
   // optional per-aggregation timing (GNN_SH_TIMING): arm the caller's event pair for the next
   // SpMM launch (gnn_spmm_set_timing_events) and record the call's shape beside it
   void arm(int64_t kind, int64_t l, int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t Fk, int64_t ldx,
-           int64_t ldo, const void* X, const void* Y, int64_t res_rows) {
+           int64_t ldo, const void* X, const void* Y, int64_t res_rows, int64_t xkind = 0) {
     if (!T || nrec >= T[0]) return;
     int64_t* r = T + 1 + GNN_STEP_TIMING_SLOTS * nrec++;
     gnn_spmm_set_timing_events((void*)r[0], (void*)r[1]);
-    const int64_t v[] = {kind, l, M, K, nnz, F, Fk, ldx, ldo, (int64_t)(uintptr_t)X, (int64_t)(uintptr_t)Y, res_rows, 1};
+    const int64_t v[] = {kind, l, M, K, nnz, F, Fk, ldx, ldo, (int64_t)(uintptr_t)X, (int64_t)(uintptr_t)Y, res_rows, 1,
+                         xkind};
     std::memcpy(r + 2, v, sizeof v);
+  }
+  // layer l's forward aggregation feat = A_l·X (armed for timing), over fp32 or 16-bit rows
+  int aggregate(int l) {
+    const LayerBufs& b = pl.lb[l];
+    arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.xk ? b.X16 : (const void*)b.X, b.feat, 0, b.xk);
+    const int32_t* rp = P<const int32_t>(d, l, GNN_SL_ROWPTR);
+    const int32_t* col = P<const int32_t>(d, l, GNN_SL_COL);
+    const float* val = P<const float>(d, l, GNN_SL_VAL);
+    if (b.xk)
+      return gnn_spmm_csr_h16_f32(rp, col, val, b.M, b.K, b.nnz, b.X16, b.ldx, b.xk, b.feat, b.ldo, b.Fk, b.ws_fwd,
+                                  b.b_fwd, 0, st);
+    return gnn_spmm_csr_f32(rp, col, val, b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk, b.ws_fwd, b.b_fwd, 0, st);
+  }
+  // xs = X[sampled] on stream s (16-bit rows widen on the way: exact)
+  int gather_sampled(int l, hipStream_t s) {
+    const LayerBufs& b = pl.lb[l];
+    const int64_t* idx = P<const int64_t>(d, l, GNN_SL_SAMPLED);
+    if (b.xk) return gnn_gather_rows_h16_f32(b.X16, b.ldx, b.xk, idx, b.xs, b.ldo, nullptr, b.M, b.F, s);
+    return gnn_gather_rows_f32(b.X, b.ldx, idx, b.xs, b.ldo, nullptr, b.M, b.F, s);
   }
   // the staging gate (GNN_SH_STAGE_EVENT): recorded right after the chosen layer's forward
   // aggregation is issued
@@ -487,18 +530,14 @@ int forward(Run& r) {
       // alone with the split choice of the pair, so the sums are those of the batched launch
       b.xs_gathered = true;
       GNN_TRY(fork_join(aux, st, aux->s));
-      GNN_TRY(gnn_gather_rows_f32(b.X, b.ldx, P<const int64_t>(d, l, GNN_SL_SAMPLED), b.xs, b.ldo, nullptr, b.M, b.F,
-                                  aux->s));
+      GNN_TRY(r.gather_sampled(l, aux->s));
       const float* Ab[1] = {b.xs};
       const float* Bb[1] = {WB};
       float* Cb[1] = {b.hB};
       GNN_TRY(gnn::gemm_split3_as_batch(0, 0, b.M, N, b.F, 1, 2, 0, Ab, b.ldo, Bb, b.F, Cb, N, b.ws_gemm_f2, b.b_gemm_f,
                                         aux->s));
       if (phase != 2 || l != 0) {
-        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
-        GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
-                                 P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
-                                 b.ws_fwd, b.b_fwd, 0, st));
+        GNN_TRY(r.aggregate(l));
         GNN_TRY(r.stage_gate(l));
       }
       const float* Aw[1] = {b.feat};
@@ -509,33 +548,26 @@ int forward(Run& r) {
     } else if (small_side) {
       b.xs_gathered = true;
       GNN_TRY(fork_join(aux, st, aux->s));  // aux sees X complete
-      GNN_TRY(gnn_gather_rows_f32(b.X, b.ldx, P<const int64_t>(d, l, GNN_SL_SAMPLED), b.xs, b.ldo, nullptr, b.M,
-                                  b.F, aux->s));
+      GNN_TRY(r.gather_sampled(l, aux->s));
       GNN_TRY(mm_xwt(ha, b.xs, b.ldo, WB, b.F, b.hB, N, b.M, N, b.F));
       if (phase != 2 || l != 0) {
-        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
-        GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
-                                 P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
-                                 b.ws_fwd, b.b_fwd, 0, st));
+        GNN_TRY(r.aggregate(l));
         GNN_TRY(r.stage_gate(l));
       }
       GNN_TRY(mm_xwt(h, b.feat, b.ldo, WW, b.F, b.hW, N, b.M, N, b.F));
       GNN_TRY(fork_join(aux, aux->s, st));  // the tail reads hB
     } else {
       if (phase != 2 || l != 0) {
-        r.arm(0, l, b.M, b.K, b.nnz, b.F, b.Fk, b.ldx, b.ldo, b.X, b.feat, 0);
-        GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, l, GNN_SL_ROWPTR), P<const int32_t>(d, l, GNN_SL_COL),
-                                 P<const float>(d, l, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
-                                 b.ws_fwd, b.b_fwd, 0, st));
+        GNN_TRY(r.aggregate(l));
         GNN_TRY(r.stage_gate(l));
       }
       // x[sampled] feeds only linearB and its weight gradient: when both run on split3 (and X's
       // rows have the aggregation output's stride) the GEMMs read X's rows through the index
       // instead of a gathered copy (bit-identical operands)
-      b.xs_gathered = !(pl.sage && ok && fills(b.M, N, n) && b.M >= 2048 && b.ldx == b.ldo && !no_index());
-      if (pl.sage && b.xs_gathered)
-        GNN_TRY(gnn_gather_rows_f32(b.X, b.ldx, P<const int64_t>(d, l, GNN_SL_SAMPLED), b.xs, b.ldo, nullptr, b.M,
-                                    b.F, st));
+      // (16-bit X0 rows are always gathered, and widened on the way: the split3 GEMMs read fp32)
+      b.xs_gathered =
+          !(pl.sage && ok && fills(b.M, N, n) && b.M >= 2048 && b.ldx == b.ldo && !no_index() && !b.xk);
+      if (pl.sage && b.xs_gathered) GNN_TRY(r.gather_sampled(l, st));
     }
     if ((big_ov && pl.sage && ok && fills(b.M, N, n)) || small_side) {
       // done above
@@ -612,10 +644,8 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
   const int64_t phase = r.phase = d[GNN_SH_PHASE];
   GNN_REQUIRE(phase >= 0 && phase <= 2, "gnn_train_step: phase %lld", (long long)phase);
   if (phase == 1) {
-    const LayerBufs& b = pl.lb[0];
-    GNN_TRY(gnn_spmm_csr_f32(P<const int32_t>(d, 0, GNN_SL_ROWPTR), P<const int32_t>(d, 0, GNN_SL_COL),
-                             P<const float>(d, 0, GNN_SL_VAL), b.M, b.K, b.nnz, b.X, b.ldx, b.feat, b.ldo, b.Fk,
-                             b.ws_fwd, b.b_fwd, 0, st));
+    r.T = nullptr;  // the prefetched aggregation is not timed
+    GNN_TRY(r.aggregate(0));
     return r.stage_gate(0);
   }
   // ------------------------------------------------------------------ forward

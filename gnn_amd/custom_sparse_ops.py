@@ -58,7 +58,9 @@ def take_timing_records(sync: bool = True):
     """Return [(tag, ms, algorithmic_bytes, kernel_name, dims)] for recorded calls and clear
     the list (kernel_name as rocprofv3 lists the main kernel: spmm_unit_kernel<VW, G, NJ, U, RES> or,
     small operands, spmm_row_kernel<VW, NJ, U, WPR, RES>;
-    dims = {M, K, nnz, F, res_rows}: the call's shape, residual rows read if any).
+    dims = {M, K, nnz, F, res_rows, x_bytes}: the call's shape, residual rows read if any, bytes per
+    gathered X element: 4, or 2 for a call that read 16-bit rows, whose kernels are
+    spmm_unit16_kernel<KIND, G, NJ, U> / spmm_row16_kernel<KIND, NJ, U, WPR>).
 
     Also folds the times into spmm_forward_time / spmm_backward_time (seconds)."""
     global spmm_forward_time, spmm_backward_time
@@ -80,23 +82,38 @@ def timing_enabled() -> bool:
     return _timing_enabled
 
 
-def record_timing(tag, e0, e1, M, K, nnz, F, Fk, ldx, ldy, xptr, yptr, unit_nnz, res_rows, residual) -> None:
+def record_timing(tag, e0, e1, M, K, nnz, F, Fk, ldx, ldy, xptr, yptr, unit_nnz, res_rows, residual,
+                  x_kind: int = 0) -> None:
     """Append one timed aggregation launch (events e0 / e1 armed around its main kernel) — also
-    used by the native step executor, whose launches are armed from C (gnn_amd.executor)."""
+    used by the native step executor, whose launches are armed from C (gnn_amd.executor).
+    x_kind 1 / 2: a gnn_spmm_csr_h16_f32 call on float16 / bfloat16 rows."""
     L = _lib.lib()
     name = ctypes.create_string_buffer(128)
+    if x_kind:  # the fp32 call's geometry at 4-wide vectors, whatever the 8-byte-aligned X allows there
+        xptr = yptr = 256
     _lib.check(L.gnn_spmm_kernel_name(M, K, nnz, Fk, ldx, ldy, xptr, yptr, unit_nnz, int(bool(residual)), name, 128),
                "gnn_spmm_kernel_name")
-    nbytes = algorithmic_bytes(M, nnz, F)
+    kname = name.value.decode()
+    if x_kind:
+        kname = _h16_kernel_name(kname, x_kind)
+    nbytes = algorithmic_bytes(M, nnz, F, 2 if x_kind else 4)
     if residual:  # residual rows read + the row map
         nbytes += res_rows * F * 4 + M * 4
-    _timing_records.append((tag, e0, e1, nbytes, name.value.decode(),
-                            dict(M=M, K=K, nnz=nnz, F=F, res_rows=res_rows if residual else 0)))
+    _timing_records.append((tag, e0, e1, nbytes, kname,
+                            dict(M=M, K=K, nnz=nnz, F=F, res_rows=res_rows if residual else 0,
+                                 x_bytes=2 if x_kind else 4)))
 
 
-def algorithmic_bytes(M: int, nnz: int, F: int) -> int:
-    """gathered X rows + (col, val) + rowptr + Y write."""
-    return nnz * F * 4 + nnz * 8 + (M + 1) * 4 + M * F * 4
+def _h16_kernel_name(fp32_name: str, kind: int) -> str:
+    """The 16-bit twin of an fp32 main kernel at VW 4 (same G / NJ / U / WPR): as rocprofv3 lists it."""
+    stem, args = fp32_name.rstrip(">").split("<")
+    a = [x.strip() for x in args.split(",")]
+    return f"{stem.replace('_kernel', '16_kernel')}<{', '.join([str(kind)] + a[1:-1])}>"
+
+
+def algorithmic_bytes(M: int, nnz: int, F: int, x_bytes: int = 4) -> int:
+    """gathered X rows (x_bytes per element) + (col, val) + rowptr + Y write."""
+    return nnz * F * x_bytes + nnz * 8 + (M + 1) * 4 + M * F * 4
 
 
 def _stream(device: torch.device) -> int:
@@ -243,15 +260,23 @@ def csr_of(mat: "torch.Tensor | CsrOperand") -> CsrOperand:
 
 def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: int = 0,
              residual: Optional[torch.Tensor] = None, rmap: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Y = A·X on the GPU. ``dense`` must be fp32, row-major rows (stride(1) == 1); a padded
-    row stride (stride(0) > F) is accepted and read in place.
+    """Y = A·X on the GPU (fp32). ``dense`` is fp32, row-major rows (stride(1) == 1); a padded
+    row stride (stride(0) > F) is accepted and read in place. A float16 / bfloat16 ``dense`` is
+    read as it is (gnn_spmm_csr_h16_f32: 4 elements per load, widened in registers, bit-identical
+    to the call on ``dense.float()``) when its rows allow it — stride a multiple of 4 elements,
+    base 8-byte aligned, F a multiple of 4 after the pad-to-4 rule below — and widened first
+    otherwise; it takes no residual.
 
     With ``rmap`` (int32[M], -1 = none) the rows ``residual[rmap[r]]`` are added to the
     output rows in the same kernel (gnn_spmm_csr_f32_ex)."""
     _require(dense.is_cuda, "denseMat must be a CUDA tensor")
     _require(dense.dim() == 2, "denseMat must be 2-D")
-    _require(dense.dtype == torch.float32, "denseMat must be float32")
+    _require(dense.dtype in FEAT_KIND, "denseMat must be float32, float16 or bfloat16")
     _require(dense.stride(1) == 1 or dense.shape[1] <= 1, "denseMat must be contiguous")
+    kind = FEAT_KIND[dense.dtype]
+    esz = dense.element_size()
+    _require(kind == FEAT_F32 or (residual is None and rmap is None),
+             "a float16 / bfloat16 denseMat takes no residual")
     M, K = op.shape
     _require(dense.shape[0] == K, f"size mismatch: sparse {tuple(op.shape)} @ dense {tuple(dense.shape)}")
     _require(dense.device == op.device, "sparseMat and denseMat must be on the same device")
@@ -269,11 +294,13 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
         _require(residual.dim() == 2 and residual.shape[1] == F and residual.stride(1) == 1,
                  "residual rows must be contiguous with F columns")
     Fk = F
-    if F % 4 and ldx % 4 == 0 and dense.data_ptr() % 16 == 0 and rmap is None:
+    if F % 4 and ldx % 4 == 0 and dense.data_ptr() % (4 * esz) == 0 and rmap is None:
         F4 = F + (4 - F % 4)
-        avail = dense.untyped_storage().nbytes() // 4 - dense.storage_offset()
+        avail = dense.untyped_storage().nbytes() // esz - dense.storage_offset()
         if ldx >= F4 and (K - 1) * ldx + F4 <= avail:
             Fk = F4
+    if kind != FEAT_F32 and (Fk % 4 or ldx % 4 or dense.data_ptr() % 8):
+        return spmm_csr(op, dense.float(), tag=tag, unit_nnz=unit_nnz)  # rows that do not fit: widen first
     # A padded input gets an output with the same row stride (line-aligned rows for the
     # consumer GEMM and whole-line row stores).
     ldo = ldx if (Fk != F and ldx <= 2 * Fk) else Fk
@@ -292,8 +319,12 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
             e1.record()
             L.gnn_spmm_set_timing_events(e0.cuda_event, e1.cuda_event)
             record_timing(tag, e0, e1, M, K, op.nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), unit_nnz,
-                          residual.shape[0] if rmap is not None else 0, rmap is not None)
-        if rmap is None:
+                          residual.shape[0] if rmap is not None else 0, rmap is not None, x_kind=kind)
+        if kind != FEAT_F32:
+            _lib.check(L.gnn_spmm_csr_h16_f32(_ptr(op.rowptr), _ptr(op.col), _ptr(op.val), M, K, op.nnz,
+                                              dense.data_ptr(), ldx, kind, out.data_ptr(), ldo, Fk,
+                                              ws.data_ptr(), wsb, unit_nnz, st), "gnn_spmm_csr_h16_f32")
+        elif rmap is None:
             _lib.check(L.gnn_spmm_csr_f32(_ptr(op.rowptr), _ptr(op.col), _ptr(op.val), M, K, op.nnz,
                                           dense.data_ptr(), ldx, out.data_ptr(), ldo, Fk,
                                           ws.data_ptr(), wsb, unit_nnz, st), "gnn_spmm_csr_f32")
@@ -321,15 +352,18 @@ class SparseDenseMM(torch.autograd.Function):
             # custom_sparse_ops.py:25 (the reference's CPU expression)
             _require(mat1.is_sparse, "sparseMat must be a sparse COO tensor")
             ctx.cpu_mat1 = mat1
-            return torch.sparse.mm(mat1, mat2)
+            ctx.x16 = mat2.dtype != torch.float32  # a 16-bit feature table: widened, no gradient for it
+            return torch.sparse.mm(mat1, mat2.float() if ctx.x16 else mat2)
         op = csr_of(mat1)
         _require(mat2.is_cuda, "denseMat must be a CUDA tensor")
         ctx.op = op
+        # a float16 / bfloat16 mat2 is a feature table: read as it is, fp32 out, no gradient for it
+        ctx.x16 = mat2.dtype != torch.float32
         return spmm_csr(op, mat2, tag="fwd")
 
     @staticmethod
     def backward(ctx, grad_output):
-        if not ctx.needs_input_grad[1]:
+        if not ctx.needs_input_grad[1] or getattr(ctx, "x16", False):
             return None, None
         if getattr(ctx, "cpu_mat1", None) is not None:
             # custom_sparse_ops.py:36, with the coalesce() torch needs for a transposed COO

@@ -29,7 +29,7 @@ VERSION, MAX_LAYERS, HEADER, LAYER_SLOTS, SAGE, GCN = 1, 4, 24, 32, 0, 1
 LOSS_BCE, LOSS_CE = 0, 1
 TIMING_SLOTS = 16
 (L_ROWPTR, L_COL, L_VAL, L_M, L_K, L_NNZ, L_TROWPTR, L_TCOL, L_TVAL, L_SAMPLED, L_NSAMPLED, L_RMAP, L_WW, L_BW,
- L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED) = range(25)
+ L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED, L_XKIND) = range(26)
 
 
 def _p(t: Optional[torch.Tensor]) -> int:
@@ -115,8 +115,14 @@ class NativeStep:
         ``labels`` may be None (predict)."""
         from .custom_sparse_ops import CsrOperand
 
-        if not (x0.is_cuda and x0.dtype == torch.float32 and x0.stride(1) == 1):
+        if not (x0.is_cuda and x0.dtype in cso.FEAT_KIND and x0.stride(1) == 1):
             return False
+        if x0.dtype != torch.float32:
+            # a 16-bit X0 (a keep16 feature store's): layer 0 aggregates from it as it is, 4 elements
+            # per load — 8-byte aligned rows with room for F rounded up to 4 (GNN_SL_XKIND)
+            ld = x0.stride(0) if x0.shape[0] > 1 else x0.shape[1]
+            if x0.data_ptr() % 8 or ld % 4 or ld < (x0.shape[1] + 3) // 4 * 4:
+                return False
         C, D = self.model.linear.weight.shape
         if C > 256 or D % 4 or D > 2048:  # the fused head's contract (fused.head_supported)
             return False
@@ -272,6 +278,7 @@ class NativeStep:
         d[H_X0], d[H_LDX0], d[H_F0] = x0.data_ptr(), x0.stride(0) if x0.shape[0] > 1 else x0.shape[1], x0.shape[1]
         if labels is not None:
             d[H_LABELS], d[H_LDL] = labels.data_ptr(), labels.stride(0) if labels.shape[0] > 1 else labels.shape[1]
+        d[HEADER + L_XKIND] = cso.FEAT_KIND[x0.dtype]
         d[H_TRAINING] = int(tr)
         # the Python path draws one seed per layer tail, then one for the head (fused.py): one
         # randint call for all of them gives the same values from the CPU generator (one call
@@ -318,4 +325,4 @@ class NativeStep:
                 continue
             kind, l, M, K, nnz, F, Fk, ldx, ldy, xp, yp, res = (int(v) for v in r[2:14])
             cso.record_timing(("fwd" if kind == 0 else "bwd") + f"_L{l}", e0, e1, M, K, nnz, F, Fk, ldx, ldy, xp, yp,
-                              0, res, kind == 1 and res > 0)
+                              0, res, kind == 1 and res > 0, x_kind=int(r[15]))

@@ -102,7 +102,8 @@ class SageAggregateFn(torch.autograd.Function):
         # input), so the pair of linear products runs as one batched GEMM
         F = x.shape[1]
         ld = feat.stride(0) if feat.dim() == 2 and feat.shape[0] > 1 else F
-        xs = torch.empty((sampled.numel(), ld), dtype=x.dtype, device=x.device)[:, :F]
+        # (a float16 / bfloat16 x, the X0 of a keep16 store: read as it is above, widened here)
+        xs = torch.empty((sampled.numel(), ld), dtype=torch.float32, device=x.device)[:, :F]
         cso.gather_rows(x, sampled, xs, None, n=sampled.numel())
         ctx.op = op
         ctx.rmap = getattr(sampled, "_gnn_rmap", None)  # precomputed by HostBatch.to_device

@@ -193,7 +193,7 @@ STAGE_SLOTS, STAGE_OUT_SLOTS, BLOB_MAX_LAYERS = 24, 6, 16
 (ST_DESC, ST_HOST_BLOB, ST_DEV_BLOB, ST_UPLOAD, ST_BUFFER, ST_LD_BUFFER, ST_X0, ST_LD_X0, ST_F, ST_INDPTR, ST_INDICES,
  ST_DEGREE, ST_NUM_NODES, ST_INDPTR_T, ST_INDICES_T, ST_ERR, ST_ERR_HOST, ST_GATE, ST_CSC_FROM, ST_ARENA,
  ST_ARENA_BYTES) = range(21)
-ST_FEAT_KIND = 21
+ST_FEAT_KIND, ST_X0_KIND = 21, 22
 SO_ROWPTR, SO_COL, SO_VAL, SO_ROWS_T, SO_VAL_T = range(5)
 _I32, _I64, _F32 = np.dtype(np.int32), np.dtype(np.int64), np.dtype(np.float32)
 _TDT = {_I32: torch.int32, _I64: torch.int64, _F32: torch.float32}
@@ -376,6 +376,8 @@ class NativeBatch:
         buf = store.gpu_buffer
         a[ST_BUFFER], a[ST_LD_BUFFER] = buf.data_ptr(), buf.stride(0)
         a[ST_FEAT_KIND] = store.kind  # 16-bit stores: the widening gather; checked against the blob's kind
+        # a keep16 store's X0 keeps the 16-bit rows (copied as whole words; its stride counts elements)
+        a[ST_X0_KIND] = store.kind if x0.dtype != torch.float32 else 0
         a[ST_X0], a[ST_LD_X0], a[ST_F] = x0.data_ptr(), x0.stride(0), x0.shape[1]
         err_host = None
         if graph is not None:

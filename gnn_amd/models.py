@@ -23,6 +23,12 @@ def _default_spmm(adj, x):
     return custom_sparse_ops.spmm(adj, x)
 
 
+def _f32(x):
+    """A float16 / bfloat16 layer-0 input (the X0 of a keep16 feature store) widened where a dense
+    torch operator reads it; the aggregation reads the 16-bit rows themselves and returns fp32."""
+    return x if x.dtype == torch.float32 else x.float()
+
+
 class GraphSageConvolution(nn.Module):
     """models.py:6-25: cat[linearB(x[self]), linearW(A·x)] -> ELU -> row standardise."""
 
@@ -40,9 +46,9 @@ class GraphSageConvolution(nn.Module):
     def forward(self, x, adj, sampled_nodes):
         if self.order > 0:
             feat = self.spmm_fn(adj, x)
-            feat = torch.cat([self.linearB(x[sampled_nodes]), self.linearW(feat)], 1)
+            feat = torch.cat([self.linearB(_f32(x[sampled_nodes])), self.linearW(feat)], 1)
         else:
-            feat = self.linearW(x)
+            feat = self.linearW(_f32(x))
         out = F.elu(feat)
         mean = out.mean(dim=1).view(out.shape[0], 1)
         var = out.var(dim=1, unbiased=False).view(out.shape[0], 1) + 1e-9
@@ -56,10 +62,10 @@ class GraphSageConvolution(nn.Module):
             if self.spmm_fn is _default_spmm:
                 feat, xs = sage_aggregate(adj, x, sampled_nodes)
             else:
-                feat, xs = self.spmm_fn(adj, x), index_rows(x, sampled_nodes)
+                feat, xs = self.spmm_fn(adj, x), index_rows(_f32(x), sampled_nodes)
             hB, hW = linear_pair([xs, feat], [self.linearB.weight, self.linearW.weight])
             return sage_norm(hB, hW, self.scale, self.offset, p, training, bB, bW)
-        (hW,) = linear_pair([x], [self.linearW.weight])
+        (hW,) = linear_pair([_f32(x)], [self.linearW.weight])
         return sage_norm(None, hW, self.scale, self.offset, p, training, None, bW)
 
 
@@ -100,9 +106,7 @@ class GraphConvolution(nn.Module):
         self.spmm_fn = spmm_fn or _default_spmm
 
     def forward(self, x, adj):
-        feat = x
-        if self.order > 0:
-            feat = self.spmm_fn(adj, feat)
+        feat = self.spmm_fn(adj, x) if self.order > 0 else _f32(x)
         out = F.elu(self.linear(feat))
         mean = out.mean(dim=1).view(out.shape[0], 1)
         var = out.var(dim=1, unbiased=False).view(out.shape[0], 1) + 1e-9
@@ -111,7 +115,7 @@ class GraphConvolution(nn.Module):
     def forward_fused(self, x, adj, p, training):
         from .fused import linear_pair, sage_norm
 
-        feat = self.spmm_fn(adj, x) if self.order > 0 else x
+        feat = self.spmm_fn(adj, x) if self.order > 0 else _f32(x)
         (h,) = linear_pair([feat], [self.linear.weight])
         return sage_norm(None, h, self.scale, self.offset, p, training, None, self.linear.bias)
 

@@ -32,6 +32,9 @@ Here (DESIGN.md §Feature staging):
     buffer, pinned host rows and peer rows keep the table's dtype and every gather above widens
     to fp32 on the way (gnn_gather_rows_h16_f32 / gnn_gather_rows2_h16_f32) — main.py:132-134's
     ``.float()``, exact, so X0 is ``feats.float()[input_nodes]`` bit for bit.
+    With ``FeatureStore(keep16=True)`` X0 itself stays 16-bit — ``feats[input_nodes]`` bit for bit in
+    ``ld_rows``-element rows, every gather a copy of whole-word rows — and the step's layer 0
+    aggregates from it as it is (gnn_spmm_csr_h16_f32).
 """
 from __future__ import annotations
 
@@ -110,10 +113,14 @@ class FeatureStore:
     pinned host rows and over the peer links; the X0 gathers widen it (exactly) to fp32, the
     ``.float()`` of main.py:132-134. ``ld`` is X0's stride in floats either way; ``ld_rows`` is
     the stride of buffer and host rows in their own elements: ``ld`` for fp32, F rounded up to 64
-    (whole 128-byte lines, never below ``ld``) for 16-bit stores."""
+    (whole 128-byte lines, never below ``ld``) for 16-bit stores.
+
+    ``keep16`` (16-bit tables only): X0 is staged in the table's dtype, ``ld_rows`` elements a row,
+    and never widened — the model's layer 0 reads the 16-bit rows (half the gather bytes, half
+    X0's memory; the results are those of the widened X0 bit for bit)."""
 
     def __init__(self, feat_data: torch.Tensor, buffer_nodes: np.ndarray, device, rank: int = 0,
-                 pin_host: bool = False, zero_copy: bool = False):
+                 pin_host: bool = False, zero_copy: bool = False, keep16: bool = False):
         if feat_data.dtype not in cso.FEAT_KIND or feat_data.dim() != 2:
             raise ValueError("FeatureStore: the feature table must be a 2-D float32, float16 or bfloat16 tensor, "
                              f"got {feat_data.dtype} with {feat_data.dim()} dimensions")
@@ -122,6 +129,9 @@ class FeatureStore:
         if zero_copy and self.kind != cso.FEAT_F32:
             raise ValueError(f"FeatureStore(zero_copy=True) reads fp32 tables only (got {self.dtype}): "
                              "16-bit stores stage through the pinned host-row copy")
+        if keep16 and self.kind == cso.FEAT_F32:
+            raise ValueError("FeatureStore(keep16=True) needs a float16 or bfloat16 table (got float32)")
+        self.keep16 = bool(keep16)
         self.device = torch.device(device)
         self.rank = rank
         self.F = int(feat_data.shape[1])
@@ -204,6 +214,16 @@ def make_plan(host_batch, store: FeatureStore, rank: int, world_size: int, devic
     return StagePlan(host_batch.num_input_nodes, own_pos, own_src, host_pos, host_rows, peer_pos, peer_src, pin)
 
 
+def word_rows(t: torch.Tensor) -> torch.Tensor:
+    """16-bit rows of whole 4-byte words (a keep16 X0, a 16-bit buffer or host rows: ``ld_rows``
+    elements, a multiple of 64) seen as fp32 rows of half as many columns, so the fp32 gathers copy
+    them element for element."""
+    if t.dim() != 2 or t.element_size() != 2 or t.stride(1) != 1 or t.shape[1] % 2 or t.stride(0) % 2 \
+            or t.data_ptr() % 4:
+        raise RuntimeError(f"16-bit rows of {tuple(t.shape)} elements (stride {t.stride(0)}) are not whole words")
+    return t.view(torch.float32)
+
+
 def _staging_stream(device):
     """The staging stream: a plain torch stream, or with GNN_STAGE_CUS = n a stream whose kernels
     run on n of the device's CUs only (gnn_stream_create_cu_masked; experiments: the X0 gathers and
@@ -264,7 +284,10 @@ class Stager:
         # No wait on the compute stream: staging only reads static buffers and its own
         # uploads, so batch i+1's X0 assembles while batch i computes.
         with torch.cuda.stream(st):
-            x0 = torch.empty((plan.n_input, self.store.ld), dtype=torch.float32, device=dev)
+            if self.store.keep16:  # X0 keeps the store's 16-bit rows; every gather below is a copy
+                x0 = torch.empty((plan.n_input, self.store.ld_rows), dtype=self.store.dtype, device=dev)
+            else:
+                x0 = torch.empty((plan.n_input, self.store.ld), dtype=torch.float32, device=dev)
             if _NATIVE_STAGE and plan.blob is not None and self.timing is None and not self.store.zero_copy:
                 from .loader import ToDevice
 
@@ -303,14 +326,18 @@ class Stager:
                 # beside the MFMA-bound GEMMs and tails instead of competing for L2 with the gather
                 st.wait_event(self.gate)
             host_rows_here = nh and (plan.host_rows is not None or (plan.blob is not None and not self.store.zero_copy))
+            # (a keep16 X0: the same gathers over the 16-bit rows as fp32 words, i.e. copies)
+            buf, x0w = self.store.gpu_buffer, x0
+            if self.store.keep16:
+                buf, x0w = word_rows(buf), word_rows(x0)
+                host_dev = word_rows(host_dev) if host_rows_here else host_dev
             if host_rows_here and _GATHER2:
                 # the own-buffer rows and the host rows in one launch (gnn_gather_rows2_f32)
-                cso.gather_rows2(self.store.gpu_buffer, own_src, own_pos, len(plan.own_pos), host_dev, None, host_pos,
-                                 nh, x0)
+                cso.gather_rows2(buf, own_src, own_pos, len(plan.own_pos), host_dev, None, host_pos, nh, x0w)
             else:
-                cso.gather_rows(self.store.gpu_buffer, own_src, x0, own_pos, n=len(plan.own_pos))
+                cso.gather_rows(buf, own_src, x0w, own_pos, n=len(plan.own_pos))
                 if host_rows_here:
-                    cso.gather_rows(host_dev, None, x0, host_pos, n=nh)
+                    cso.gather_rows(host_dev, None, x0w, host_pos, n=nh)
             extra = ()
             if self.exchange is not None:
                 extra = self.exchange.exchange(plan, x0, self.store, meta)
@@ -521,7 +548,10 @@ class PeerExchange:
         self.dist.all_to_all_single(recv_rows, send_rows, output_split_sizes=sc, input_split_sizes=rc,
                                     group=self.group)
         if sum(sc):
-            cso.gather_rows(recv_rows, None, x0, pos, n=sum(sc))
+            if x0.dtype != torch.float32:  # a keep16 X0 takes the rows as they travelled (whole words)
+                cso.gather_rows(word_rows(recv_rows), None, word_rows(x0), pos, n=sum(sc))
+            else:
+                cso.gather_rows(recv_rows, None, x0, pos, n=sum(sc))
         return (want, pos, send_rows, recv_rows)
 
 
@@ -687,6 +717,16 @@ class PeerDirect:
                 pos = torch.from_numpy(np.ascontiguousarray(plan.peer_pos[j], np.int64)).to(dev, non_blocking=True)
                 src = torch.from_numpy(np.ascontiguousarray(plan.peer_src[j], np.int64)).to(dev, non_blocking=True)
             keep += [pos, src]
+            if x0.dtype != torch.float32:
+                # a keep16 X0: the peer's 16-bit rows as they are, whole words copied by the fp32 gather
+                if ld % 2 or x0.stride(0) % 2 or x0.shape[1] % 2:
+                    raise RuntimeError(f"PeerDirect: 16-bit rows of {ld} / {x0.stride(0)} elements are not whole words")
+                with _lib.on_device(dev):
+                    _lib.check(_lib.lib().gnn_gather_rows_f32(ptr, ld // 2, src.data_ptr(), x0.data_ptr(),
+                                                              x0.stride(0) // 2, pos.data_ptr(), n,
+                                                              min(ld, x0.shape[1]) // 2, _lib.stream_of(dev)),
+                               "gnn_gather_rows (peer, 16-bit copy)")
+                continue
             self._gather(ptr, ld, src.data_ptr(), x0.data_ptr(), x0.stride(0), pos.data_ptr(), n,
                          min(ld, x0.shape[1]), "gnn_gather_rows (peer)")
         return tuple(keep)

@@ -87,7 +87,32 @@ int gnn_spmm_kernel_name(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t l
                          const void* X, const void* Y, int64_t unit_nnz, int residual, char* out,
                          size_t out_bytes);
 
-/* Optional timing hook: when set, the NEXT gnn_spmm_csr_f32 call on this thread launches its
+/* The same aggregation reading X as 16-bit rows (kind = GNN_FEAT_F16 or GNN_FEAT_BF16, declared
+ * with the feature gathers below; ldx in 16-bit elements): Y = A · (float)X without an fp32 copy
+ * of X — layer 0 straight from a 16-bit feature store's staged rows. A lane loads 4 elements
+ * (8 bytes) where the fp32 kernel loads a float4 and widens them in registers (both conversions
+ * exact); lane groups, column tiles, unit size, row / unit kernel choice and workgroup order are
+ * those gnn_spmm_csr_f32 takes for the same (M, K, nnz, F) with 4-wide vectors, so Y equals that
+ * call's result on the widened X bit for bit. Same contract (stream-ordered, no allocation, no
+ * host synchronisation, graph-capturable, timing hook honoured) and same workspace size
+ * (gnn_spmm_workspace_bytes). There is no scalar form and no residual: refused with GNN_EINVAL
+ * before anything is launched are a kind other than 1 or 2, an X that is not 8-byte aligned, a Y
+ * that is not 16-byte aligned, ldx, ldy or F not a multiple of 4, and F > ldx or F > ldy — a
+ * caller whose rows do not fit widens them first. */
+int gnn_spmm_csr_h16_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                         int64_t M, int64_t K, int64_t nnz,
+                         const void* X, int64_t ldx, int kind,
+                         float* Y, int64_t ldy, int64_t F,
+                         void* workspace, size_t workspace_bytes, int64_t unit_nnz,
+                         void* stream);
+
+/* The configuration gnn_spmm_csr_h16_f32 would pick: out[0..5] as gnn_spmm_config (out[0] = 4),
+ * out[6] = waves per row of the row kernel (0: the unit kernel), out[7] = 16-bit elements per
+ * load. X / Y are read for nothing here (the call itself checks their alignment). */
+int gnn_spmm_h16_config(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, int64_t ldy,
+                        const void* X, const void* Y, int64_t unit_nnz, int32_t out[8]);
+
+/* Optional timing hook: when set, the NEXT gnn_spmm_csr_f32 / gnn_spmm_csr_h16_f32 call on this thread launches its
  * main aggregation kernel with `start` / `stop` as the dispatch's own start and end timestamps
  * (hipExtLaunchKernel: hipEventElapsedTime(start, stop) = the kernel's duration, as rocprofv3
  * reports it), then clears the hook. Events are hipEvent_t (created with timing) as void*. */

@@ -27,6 +27,14 @@
  *                                 are GNN_H_LD_HOST_ROWS 16-bit elements wide, and X0 is gathered by
  *                                 gnn_gather_rows2_h16_f32. It must equal the blob's GNN_H_FEAT_KIND:
  *                                 a mismatch is refused (by gnn_stage_plan too) before the upload
+ *   X0_KIND                       0: X0 is fp32 (the above). Otherwise it must equal FEAT_KIND (GNN_FEAT_F16
+ *                                 / GNN_FEAT_BF16; a mismatch is refused by gnn_stage_plan and by the
+ *                                 call before the upload): X0 keeps the store's 16-bit elements for a
+ *                                 step that aggregates from them (gnn_step.h GNN_SL_XKIND); LD_X0 then
+ *                                 counts elements and equals the blob's GNN_H_LD_HOST_ROWS, F is the
+ *                                 width copied in elements, and the rows are copied as they are by
+ *                                 gnn_gather_rows2_f32 over the rows as fp32 words (every stride and F
+ *                                 even); X0's pad columns come out zero because the sources' are
  *   INDPTR, INDICES, DEGREE, NUM_NODES, INDPTR_T, INDICES_T, ERR
  *                                 the graph on the device (sampler.DeviceGraph) for GPU-extracted
  *                                 layers, and its error flag; ERR_HOST: pinned int32 the flag is
@@ -61,7 +69,7 @@ enum {
   GNN_ST_LD_BUFFER = 5, GNN_ST_X0 = 6, GNN_ST_LD_X0 = 7, GNN_ST_F = 8, GNN_ST_INDPTR = 9, GNN_ST_INDICES = 10,
   GNN_ST_DEGREE = 11, GNN_ST_NUM_NODES = 12, GNN_ST_INDPTR_T = 13, GNN_ST_INDICES_T = 14, GNN_ST_ERR = 15,
   GNN_ST_ERR_HOST = 16, GNN_ST_GATE = 17, GNN_ST_CSC_FROM = 18, GNN_ST_ARENA = 19, GNN_ST_ARENA_BYTES = 20,
-  GNN_ST_FEAT_KIND = 21
+  GNN_ST_FEAT_KIND = 21, GNN_ST_X0_KIND = 22
 };
 
 enum { GNN_SO_ROWPTR = 0, GNN_SO_COL = 1, GNN_SO_VAL = 2, GNN_SO_ROWS_T = 3, GNN_SO_VAL_T = 4, GNN_SO_WORKSPACE = 5 };

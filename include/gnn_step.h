@@ -21,8 +21,9 @@
  *     optionally timing: a HOST int64 array T, T[0] = capacity in records, then records of
  *     GNN_STEP_TIMING_SLOTS slots; the caller puts a hipEvent_t pair in slots 0-1 of each, and
  *     the step arms them around its aggregation kernels in call order (forward layers bottom-up,
- *     then the backward aggregations top-down) and writes slots 2-14: kind (0 fwd, 1 bwd),
- *     layer, M, K, nnz, F, padded F, ldx, ldy, X, Y (device addresses), residual rows, 1;
+ *     then the backward aggregations top-down) and writes slots 2-15: kind (0 fwd, 1 bwd),
+ *     layer, M, K, nnz, F, padded F, ldx, ldy, X, Y (device addresses), residual rows, 1, the
+ *     element kind of X (GNN_SL_XKIND);
  *     and optionally gradient-ready events: a HOST int64 array E, E[0] = entries, E[1] = a
  *     hipEvent_t recorded once the head's gradients are final, E[2 + l] = one recorded once
  *     layer l's gradients (weights, biases, scale, offset) are final (0 = none): the caller's
@@ -46,6 +47,17 @@
  *     sampled (int64 [M], SAGE) and rmap (int32 [K], rmap[sampled[i]] = i, SAGE layers >= 1),
  *     weights W_W / W_B (N x F row-major), biases, scale / offset, their gradient buffers, the
  *     dropout seed. Layer l >= 1 reads layer l-1's output (K_l must equal M_{l-1}).
+ *     GNN_SL_XKIND: the element kind of the layer's input (gnn_spmm.h GNN_FEAT_*). 0 = fp32, so
+ *     every descriptor built before the slot had a meaning keeps it (GNN_STEP_VERSION stays 1).
+ *     GNN_FEAT_F16 / GNN_FEAT_BF16 are allowed on layer 0 only: GNN_SH_X0 is then a 16-bit pointer
+ *     (8-byte aligned) and GNN_SH_LDX0 counts elements (a multiple of 4, with room for F0 rounded up
+ *     to 4). The layer-0 aggregation reads those rows as they are (gnn_spmm_csr_h16_f32, also in
+ *     phase 1; bit-identical to the fp32 call on the widened rows), into rows of F0 rounded up to 4
+ *     and then to 32 floats — the stride of the fp32 X0 a feature store stages today, so the
+ *     workspace is the widened step's; SAGE's x[sampled] is gathered and widened into the layer's
+ *     xs buffer (gnn_gather_rows_h16_f32) for linearB and its weight gradient: the split3 GEMMs do
+ *     not read 16-bit rows in place. Any other value, or a non-zero kind on a layer >= 1, is
+ *     refused like a bad loss kind: both *_workspace_bytes functions return 0, nothing is launched.
  */
 #ifndef GNN_STEP_H
 #define GNN_STEP_H
@@ -79,7 +91,7 @@ enum {
   GNN_SL_TROWPTR = 6, GNN_SL_TCOL = 7, GNN_SL_TVAL = 8, GNN_SL_SAMPLED = 9, GNN_SL_NSAMPLED = 10,
   GNN_SL_RMAP = 11, GNN_SL_WW = 12, GNN_SL_BW = 13, GNN_SL_WB = 14, GNN_SL_BB = 15, GNN_SL_SCALE = 16,
   GNN_SL_OFFSET = 17, GNN_SL_GWW = 18, GNN_SL_GBW = 19, GNN_SL_GWB = 20, GNN_SL_GBB = 21, GNN_SL_GSCALE = 22,
-  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24
+  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24, GNN_SL_XKIND = 25
 };
 
 size_t gnn_train_step_workspace_bytes(const int64_t* desc);
