@@ -27,6 +27,10 @@
 //                         dW_B, dW_W = [dhB, dhW]ᵀ·[xs, feat]  (split-k split3 from 2048 rows)
 //                         l >= 1: dxs, dfeat = [dhB, dhW]·[W_B, W_W];
 //                                 dY_{l-1} = A_lᵀ·dfeat (+ dxs scattered through rmap, SAGE)
+//   an order-0 layer (GNN_SL_DENSE, models.py:21, 59-60) has no operand:
+//   forward:              hW = X·W_Wᵀ (X in place);  Y_l = sage_norm(hW + b_W), width N
+//   backward:             dhW, dscale, doffset, dbW = sage_norm_bwd(dY_l);  dW_W = dhWᵀ·X;
+//                         l >= 1: dY_{l-1} = dhW·W_W, written straight into that buffer
 //
 // gnn_eval_step_f32 (validation / test batches, main.py:178-199, 217-241) is the forward above
 // with training = 0 — forward() below, called by both entry points — followed by the evaluation
@@ -238,6 +242,10 @@ int mm_gtx(rocblas_handle h, const float* g, int64_t ldg, const float* x, int64_
 struct LayerBufs {
   int64_t M, K, nnz, F, Fk, ldx, ldo, N, D;
   bool xs_gathered;  // false: x[sampled] is read in place by the split3 GEMMs (row-indexed X)
+  // an order-0 layer (GNN_SL_DENSE): no operand, Y = sage_norm(X·W_Wᵀ) of width D = N; X is read in
+  // place (a 16-bit X0 widened once into feat, rows of ldo floats), and the input gradient dhW·W_W
+  // is written straight into the layer below's dY
+  bool dense;
   const float* X;
   // layer 0 over a 16-bit X0 (GNN_SL_XKIND = GNN_FEAT_F16 / GNN_FEAT_BF16): X is NULL, X16 the rows
   // (ldx in elements); the aggregation reads them as they are and x[sampled] is widened into xs
@@ -252,6 +260,9 @@ struct LayerBufs {
   bool dy_agg;
   const int32_t *agg_rp, *agg_col, *agg_rmap;
   const float *agg_val, *agg_G, *agg_R;
+  // the fp32 rows an order-0 layer's products read, and their stride
+  const float* in() const { return xk ? feat : X; }
+  int64_t ldin() const { return xk ? ldo : ldx; }
 };
 
 struct Plan {
@@ -289,7 +300,16 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
     b.K = L(d, l, GNN_SL_K);
     b.nnz = L(d, l, GNN_SL_NNZ);
     b.N = N;
-    b.D = n * N;
+    const int64_t dense = L(d, l, GNN_SL_DENSE);
+    GNN_REQUIRE(dense == 0 || dense == 1, "gnn_train_step: layer %d dense flag %lld (0: aggregating, 1: order 0)", l,
+                (long long)dense);
+    b.dense = dense != 0;
+    b.D = b.dense ? N : n * N;
+    if (b.dense) {
+      GNN_REQUIRE(b.K == b.M, "gnn_train_step: order-0 layer %d has K = %lld, M = %lld", l, (long long)b.K,
+                  (long long)b.M);
+      b.nnz = 0;  // no operand: the slot is ignored
+    }
     const int64_t xk = L(d, l, GNN_SL_XKIND);
     GNN_REQUIRE(xk == GNN_FEAT_F32 || (l == 0 && (xk == GNN_FEAT_F16 || xk == GNN_FEAT_BF16)),
                 "gnn_train_step: layer %d input kind %lld (0: fp32; 1 fp16 / 2 bf16 on layer 0 only)", l,
@@ -328,8 +348,8 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
                   (long long)b.ldx, (long long)b.Fk);
       b.ldo = (int64_t)align_up((size_t)b.Fk, 32);
     }
-    b.b_fwd = gnn_spmm_workspace_bytes(b.M, b.nnz, b.Fk, 0);
-    b.b_gemm_f = gemm_ws(b.M, N, b.F, n);
+    b.b_fwd = b.dense ? 0 : gnn_spmm_workspace_bytes(b.M, b.nnz, b.Fk, 0);
+    b.b_gemm_f = gemm_ws(b.M, N, b.F, b.dense ? 1 : n);
   }
   const LayerBufs& top = pl.lb[pl.nl - 1];
   pl.Mh = top.M;
@@ -346,11 +366,15 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
 // it again from the step's stream, so no buffer is rewritten while the other stream may read it.
 int plan_eval(const int64_t* d, Arena& ar, Plan& pl) {
   GNN_TRY(shapes(d, !ar.base, pl));
-  int64_t feat = 0, h = 0, rows = 0, y[2] = {0, 0};
+  int64_t feat = 0, xs = 0, h = 0, rows = 0, y[2] = {0, 0};
   size_t wf = 0, wg = 0;
+  bool agg = false;  // any aggregating layer: feat, the SpMM workspace and (SAGE) xs, hB, the aux product
   for (int l = 0; l < pl.nl; ++l) {
     const LayerBufs& b = pl.lb[l];
-    feat = std::max(feat, b.M * b.ldo);
+    agg = agg || !b.dense;
+    // an order-0 layer reads X in place: no feat (but the widened rows of a 16-bit X0)
+    if (!b.dense || b.xk) feat = std::max(feat, b.M * b.ldo);
+    if (!b.dense) xs = std::max(xs, b.M * b.ldo);
     h = std::max(h, b.M * b.N);
     rows = std::max(rows, b.M);
     y[l & 1] = std::max(y[l & 1], b.M * b.D);
@@ -358,16 +382,17 @@ int plan_eval(const int64_t* d, Arena& ar, Plan& pl) {
     wg = std::max(wg, b.b_gemm_f);
   }
   LayerBufs s = {};
-  s.feat = ar.take<float>(feat);
-  s.xs = pl.sage ? ar.take<float>(feat) : nullptr;
-  s.hB = pl.sage ? ar.take<float>(h) : nullptr;
+  const bool pair = pl.sage && agg;
+  s.feat = (agg || feat) ? ar.take<float>(feat) : nullptr;
+  s.xs = pair ? ar.take<float>(xs) : nullptr;
+  s.hB = pair ? ar.take<float>(h) : nullptr;
   s.hW = ar.take<float>(h);
   float* const Y[2] = {ar.take<float>(y[0]), ar.take<float>(y[1])};
   s.mean = ar.take<float>(rows);
   s.rstd = ar.take<float>(rows);
-  s.ws_fwd = ar.take<char>((int64_t)wf);
+  s.ws_fwd = agg ? ar.take<char>((int64_t)wf) : nullptr;
   s.ws_gemm_f = ar.take<char>((int64_t)wg);
-  s.ws_gemm_f2 = pl.sage ? ar.take<char>((int64_t)wg) : nullptr;
+  s.ws_gemm_f2 = pair ? ar.take<char>((int64_t)wg) : nullptr;
   for (int l = 0; l < pl.nl; ++l) {
     LayerBufs& b = pl.lb[l];
     if (l) b.X = pl.lb[l - 1].Y;
@@ -386,16 +411,17 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
   for (int l = 0; l < pl.nl; ++l) {
     LayerBufs& b = pl.lb[l];
     if (l) b.X = pl.lb[l - 1].Y;
-    b.feat = ar.take<float>(b.M * b.ldo);
-    b.xs = pl.sage ? ar.take<float>(b.M * b.ldo) : nullptr;
-    b.hB = pl.sage ? ar.take<float>(b.M * N) : nullptr;
+    const bool pair = pl.sage && !b.dense;
+    b.feat = (!b.dense || b.xk) ? ar.take<float>(b.M * b.ldo) : nullptr;
+    b.xs = pair ? ar.take<float>(b.M * b.ldo) : nullptr;
+    b.hB = pair ? ar.take<float>(b.M * N) : nullptr;
     b.hW = ar.take<float>(b.M * N);
     b.Y = ar.take<float>(b.M * b.D);
     b.mean = ar.take<float>(b.M);
     b.rstd = ar.take<float>(b.M);
-    b.ws_fwd = ar.take<char>((int64_t)b.b_fwd);
+    b.ws_fwd = b.dense ? nullptr : ar.take<char>((int64_t)b.b_fwd);
     b.ws_gemm_f = ar.take<char>((int64_t)b.b_gemm_f);
-    b.ws_gemm_f2 = pl.sage ? ar.take<char>((int64_t)b.b_gemm_f) : nullptr;  // the aux stream's product
+    b.ws_gemm_f2 = pair ? ar.take<char>((int64_t)b.b_gemm_f) : nullptr;  // the aux stream's product
   }
   pl.xd = ar.take<float>(pl.Mh * pl.Dh);
   pl.z = ar.take<float>(pl.Mh * pl.C);
@@ -406,14 +432,21 @@ int plan(const int64_t* d, Arena& ar, Plan& pl) {
   pl.dXh = ar.take<float>(pl.Mh * pl.Dh);
   for (int l = pl.nl - 1; l >= 0; --l) {
     LayerBufs& b = pl.lb[l];
-    b.dY = (l == pl.nl - 1) ? pl.dXh : pl.lb[l + 1].dfeat;  // placeholder, set below for l < nl-1
-    b.dhB = pl.sage ? ar.take<float>(b.M * N) : nullptr;
+    b.dY = (l == pl.nl - 1) ? pl.dXh : nullptr;  // set below for l < nl-1
+    b.dhB = (pl.sage && !b.dense) ? ar.take<float>(b.M * N) : nullptr;
     b.dhW = ar.take<float>(b.M * N);
     b.b_norm = gnn_sage_norm_bwd_workspace_bytes(b.M, b.D);
     b.ws_norm = ar.take<char>((int64_t)b.b_norm);
-    b.b_gemm_dw = gemm_ws(N, b.F, b.M, n);
+    b.b_gemm_dw = gemm_ws(N, b.F, b.M, b.dense ? 1 : n);
     b.ws_gemm_dw = ar.take<char>((int64_t)b.b_gemm_dw);
-    if (l >= 1) {
+    if (l >= 1 && b.dense) {
+      // the input gradient dhW·W_W goes straight into layer l-1's dY: no dfeat / dxs, no SpMM
+      b.dxs = b.dfeat = nullptr;
+      b.b_gemm_dx = gemm_ws(b.M, b.F, N, 1);
+      b.ws_gemm_dx = ar.take<char>((int64_t)b.b_gemm_dx);
+      b.ws_bwd = nullptr;
+      b.b_bwd = 0;
+    } else if (l >= 1) {
       b.dxs = pl.sage ? ar.take<float>(b.M * b.F) : nullptr;
       b.dfeat = ar.take<float>(b.M * b.F);
       b.b_gemm_dx = gemm_ws(b.M, b.F, N, n);
@@ -495,7 +528,8 @@ struct Run {
     return gnn_gather_rows_f32(b.X, b.ldx, idx, b.xs, b.ldo, nullptr, b.M, b.F, s);
   }
   // the staging gate (GNN_SH_STAGE_EVENT): recorded right after the chosen layer's forward
-  // aggregation is issued
+  // aggregation is issued; for an order-0 layer where that aggregation would have been, before
+  // the layer's GEMM
   int stage_gate(int l) {
     if (d[GNN_SH_STAGE_EVENT] && l == (int)d[GNN_SH_STAGE_LAYER])
       GNN_HIP(hipEventRecord((hipEvent_t)d[GNN_SH_STAGE_EVENT], st), "hipEventRecord (stage gate)");
@@ -519,6 +553,28 @@ int forward(Run& r) {
     const int64_t N = b.N;
     const float* WB = P<const float>(d, l, GNN_SL_WB);
     const float* WW = P<const float>(d, l, GNN_SL_WW);
+    if (b.dense) {
+      // order 0 (models.py:21, 59-60): hW = X·W_Wᵀ with X read in place, one product routed as
+      // the pairs below; then the tail in its D1 = 0 form. No operand, no x[sampled], no aux stream.
+      if (phase != 2 || l != 0) GNN_TRY(r.stage_gate(l));  // where the aggregation would have been
+      if (b.xk)  // 16-bit X0: widened once (exact), then the layer runs as fp32
+        GNN_TRY(gnn_gather_rows_h16_f32(b.X16, b.ldx, b.xk, nullptr, b.feat, b.ldo, nullptr, b.M, b.F, st));
+      const float* X = b.in();
+      const int64_t ldx = b.ldin();
+      b.xs_gathered = true;
+      if (gemm_ok(X, ldx) && gemm_ok(WW, b.F) && fills(b.M, N, 1)) {
+        const float* A[1] = {X};
+        const float* B[1] = {WW};
+        float* Cc[1] = {b.hW};
+        GNN_TRY(gemm(0, 0, b.M, N, b.F, 1, A, ldx, B, b.F, Cc, N, b.ws_gemm_f, b.b_gemm_f, st));
+      } else {
+        GNN_TRY(mm_xwt(h, X, ldx, WW, b.F, b.hW, N, b.M, N, b.F));
+      }
+      GNN_TRY(gnn_sage_norm_fwd_f32(nullptr, 4, 0, b.hW, N, N, nullptr, P<const float>(d, l, GNN_SL_BW),
+                                    P<const float>(d, l, GNN_SL_SCALE), P<const float>(d, l, GNN_SL_OFFSET), b.M, r.p,
+                                    (uint64_t)L(d, l, GNN_SL_SEED), r.training, b.Y, b.D, b.mean, b.rstd, st));
+      continue;
+    }
     if (pl.sage)
       GNN_REQUIRE(L(d, l, GNN_SL_NSAMPLED) == b.M, "gnn_train_step: layer %d sampled %lld != M %lld", l,
                   (long long)L(d, l, GNN_SL_NSAMPLED), (long long)b.M);
@@ -645,7 +701,8 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
   GNN_REQUIRE(phase >= 0 && phase <= 2, "gnn_train_step: phase %lld", (long long)phase);
   if (phase == 1) {
     r.T = nullptr;  // the prefetched aggregation is not timed
-    GNN_TRY(r.aggregate(0));
+    // an order-0 layer 0 has no aggregation to issue ahead: no kernel, only the gate if it is layer 0's
+    if (!pl.lb[0].dense) GNN_TRY(r.aggregate(0));
     return r.stage_gate(0);
   }
   // ------------------------------------------------------------------ forward
@@ -699,23 +756,67 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
     const int64_t N = b.N;
     const float* WB = P<const float>(d, l, GNN_SL_WB);
     const float* WW = P<const float>(d, l, GNN_SL_WW);
+    const bool pair = pl.sage && !b.dense;  // an order-0 layer's tail is the D1 = 0 form
     if (b.dy_agg)  // the layer above's backward aggregation, computed as this tail reads its rows
       GNN_TRY(gnn_sage_norm_bwd_agg_f32(b.agg_rp, b.agg_col, b.agg_val, b.agg_G, b.D, b.agg_R, b.D, b.agg_rmap,
-                                        pl.sage ? b.hB : nullptr, pl.sage ? N : 4, pl.sage ? N : 0, b.hW, N, N,
-                                        pl.sage ? P<const float>(d, l, GNN_SL_BB) : nullptr,
+                                        pair ? b.hB : nullptr, pair ? N : 4, pair ? N : 0, b.hW, N, N,
+                                        pair ? P<const float>(d, l, GNN_SL_BB) : nullptr,
                                         P<const float>(d, l, GNN_SL_BW), P<const float>(d, l, GNN_SL_SCALE), b.mean,
                                         b.rstd, b.M, p, (uint64_t)L(d, l, GNN_SL_SEED), training, b.dhB, b.dhW,
                                         P<float>(d, l, GNN_SL_GSCALE), P<float>(d, l, GNN_SL_GOFFSET),
-                                        pl.sage ? P<float>(d, l, GNN_SL_GBB) : nullptr, P<float>(d, l, GNN_SL_GBW),
+                                        pair ? P<float>(d, l, GNN_SL_GBB) : nullptr, P<float>(d, l, GNN_SL_GBW),
                                         b.ws_norm, b.b_norm, st));
     else
-      GNN_TRY(gnn_sage_norm_bwd_f32(b.dY, b.D, pl.sage ? b.hB : nullptr, pl.sage ? N : 4, pl.sage ? N : 0, b.hW, N, N,
-                                    pl.sage ? P<const float>(d, l, GNN_SL_BB) : nullptr, P<const float>(d, l, GNN_SL_BW),
+      GNN_TRY(gnn_sage_norm_bwd_f32(b.dY, b.D, pair ? b.hB : nullptr, pair ? N : 4, pair ? N : 0, b.hW, N, N,
+                                    pair ? P<const float>(d, l, GNN_SL_BB) : nullptr, P<const float>(d, l, GNN_SL_BW),
                                     P<const float>(d, l, GNN_SL_SCALE), b.mean, b.rstd, b.M, p,
                                     (uint64_t)L(d, l, GNN_SL_SEED), training, b.dhB, b.dhW,
                                     P<float>(d, l, GNN_SL_GSCALE), P<float>(d, l, GNN_SL_GOFFSET),
-                                    pl.sage ? P<float>(d, l, GNN_SL_GBB) : nullptr, P<float>(d, l, GNN_SL_GBW),
+                                    pair ? P<float>(d, l, GNN_SL_GBB) : nullptr, P<float>(d, l, GNN_SL_GBW),
                                     b.ws_norm, b.b_norm, st));
+    if (b.dense) {
+      // order 0: the input gradient is a GEMM, written straight into layer l-1's dY (M x F, stride
+      // F = D_{l-1}: no dfeat, no transpose, no SpMM, so nothing to fold below); the weight
+      // gradient dhWᵀ·X reads X in place. Routed as the aggregating layers' products.
+      const float* X = b.in();
+      const int64_t ldx = b.ldin();
+      const bool okd = gemm_ok(X, ldx) && gemm_ok(WW, b.F);
+      const float* Gd[1] = {b.dhW};
+      if (l >= 1) {
+        float* dYp = pl.lb[l - 1].dY;
+        if (okd && fills(b.M, b.F, 1)) {
+          const float* B[1] = {WW};
+          float* Cc[1] = {dYp};
+          GNN_TRY(gemm(0, 1, b.M, b.F, N, 1, Gd, N, B, b.F, Cc, b.F, b.ws_gemm_dx, b.b_gemm_dx, st));
+        } else {
+          GNN_TRY(mm_gw(h, b.dhW, N, WW, b.F, dYp, b.F, b.M, b.F, N));
+        }
+      }
+      float* gWW = P<float>(d, l, GNN_SL_GWW);
+      hipStream_t sw = st;
+      if (okd && b.M >= 2048) {
+        if (big_ov && l >= 1) {
+          GNN_TRY(fork_join(aux, st, aux->s));
+          sw = aux->s;
+          aux_used = true;
+        }
+        const float* Xd[1] = {X};
+        float* Cc[1] = {gWW};
+        GNN_TRY(gemm(1, 1, N, b.F, b.M, 1, Gd, N, Xd, ldx, Cc, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw));
+      } else {
+        rocblas_handle hw = h;
+        if (ha) {
+          GNN_TRY(fork_join(aux, st, aux->s));
+          sw = aux->s;
+          hw = ha;
+          aux_used = true;
+          if (head_pending) GNN_TRY(head_grads(aux->s, ha));
+        }
+        GNN_TRY(mm_gtx(hw, b.dhW, N, X, ldx, gWW, b.F, N, b.F, b.M));
+      }
+      GNN_TRY(grads_ready(2 + l, sw));
+      continue;
+    }
     const bool ok = gemm_ok(b.feat, b.ldo) && gemm_ok(WW, b.F) && (!pl.sage || gemm_ok(WB, b.F));
     const float* G[2] = {pl.sage ? b.dhB : b.dhW, b.dhW};
     const int o = pl.sage ? 0 : 1;

@@ -29,7 +29,8 @@ VERSION, MAX_LAYERS, HEADER, LAYER_SLOTS, SAGE, GCN = 1, 4, 24, 32, 0, 1
 LOSS_BCE, LOSS_CE = 0, 1
 TIMING_SLOTS = 16
 (L_ROWPTR, L_COL, L_VAL, L_M, L_K, L_NNZ, L_TROWPTR, L_TCOL, L_TVAL, L_SAMPLED, L_NSAMPLED, L_RMAP, L_WW, L_BW,
- L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED, L_XKIND) = range(26)
+ L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED, L_XKIND,
+ L_DENSE) = range(27)
 
 
 def _p(t: Optional[torch.Tensor]) -> int:
@@ -42,7 +43,8 @@ def enabled() -> bool:
 
 
 class NativeStep:
-    """Binds a fused ``models.GNN`` (GraphSage or GCN encoder, every layer of order 1) to
+    """Binds a fused ``models.GNN`` (GraphSage or GCN encoder, every layer of order 1 or 0: the
+    reference's ``--orders``, an order-0 layer is plain dense and takes ``None`` as its operand) to
     gnn_train_step_f32. ``step(x0, adjs, sampled_nodes, labels)`` runs forward + backward and
     returns the loss (a device scalar); the gradients are in the parameters' ``.grad``.
     ``evaluate(x0, adjs, sampled_nodes, labels)`` runs the forward alone through
@@ -63,8 +65,9 @@ class NativeStep:
             self.kind = GCN
         else:
             raise ValueError(f"NativeStep: unsupported encoder {type(enc).__name__}")
-        if any(g.order != 1 for g in enc.gcs) or not 1 <= len(enc.gcs) <= MAX_LAYERS:
-            raise ValueError("NativeStep: every layer must have order 1 (1-4 layers)")
+        if any(g.order not in (0, 1) for g in enc.gcs) or not 1 <= len(enc.gcs) <= MAX_LAYERS:
+            raise ValueError("NativeStep: every layer must have order 0 or 1 (1-4 layers)")
+        self.dense = [g.order == 0 for g in enc.gcs]
         self.model = model
         self.enc = enc
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters()]
@@ -94,10 +97,14 @@ class NativeStep:
         d[H_PDROP_BITS] = struct.unpack("<i", struct.pack("<f", self.p_enc))[0]
         for li, gc in enumerate(enc.gcs):
             b = HEADER + li * LAYER_SLOTS
+            d[b + L_DENSE] = int(self.dense[li])
             if self.kind == SAGE:
                 W, B = gc.linearW, gc.linearB
-                d[b + L_WB], d[b + L_BB] = _p(B.weight), _p(B.bias)
-                d[b + L_GWB], d[b + L_GBB] = _p(g[id(B.weight)]), _p(g[id(B.bias)])
+                if not self.dense[li]:
+                    # (an order-0 layer's linearB takes no part, models.py:21: its slots stay 0 and
+                    # its gradient views stay zero, as the Python path leaves its .grad None)
+                    d[b + L_WB], d[b + L_BB] = _p(B.weight), _p(B.bias)
+                    d[b + L_GWB], d[b + L_GBB] = _p(g[id(B.weight)]), _p(g[id(B.bias)])
             else:
                 W = gc.linear
             d[b + L_WW], d[b + L_BW] = _p(W.weight), _p(W.bias)
@@ -132,7 +139,13 @@ class NativeStep:
         elif not (labels.dtype == torch.float32 and labels.dim() == 2 and labels.stride(1) == 1
                   and labels.shape[1] == C):
             return False
+        if len(adjs) != len(self.dense):
+            return False
         for li, op in enumerate(adjs):
+            if self.dense[li]:
+                if op is not None:  # an order-0 layer takes no operand (the samplers hand None)
+                    return False
+                continue
             if not isinstance(op, CsrOperand):
                 return False
             if li >= 1 and op._t is None and not inference:
@@ -157,7 +170,8 @@ class NativeStep:
 
     @staticmethod
     def _batch_key(x0, adjs, labels):
-        return (x0.data_ptr(), tuple(x0.shape), x0.stride(0), labels.data_ptr(), tuple(id(op) for op in adjs))
+        return (x0.data_ptr(), tuple(x0.shape), x0.stride(0), labels.data_ptr(),
+                tuple(id(op) for op in adjs if op is not None))
 
     def prefetch(self, x0, adjs, sampled_nodes, labels, stage_gate=None) -> None:
         """Issue ONLY this batch's layer-0 forward aggregation A_0·x0 (GNN_SH_PHASE 1) into a
@@ -166,7 +180,11 @@ class NativeStep:
         batch, never a parameter, so a data-parallel trainer issues it between the gradient
         all-reduce's launch and the optimizer step: it runs while the all-reduce does (reference:
         main.py:122-168, where the next batch's forward starts after the exchange and the step).
-        No dropout seed is drawn here: the step draws them, in the same order as without it."""
+        No dropout seed is drawn here: the step draws them, in the same order as without it.
+        With an order-0 layer 0 there is no aggregation to issue ahead: nothing is done, and the
+        step records the staging gate itself."""
+        if self.dense[0]:
+            return
         d = self._desc(x0, adjs, sampled_nodes, labels, seeds=False)
         if stage_gate is not None and int(stage_gate[1]) == 0:
             self._set_gate(d, stage_gate)
@@ -259,7 +277,7 @@ class NativeStep:
             counts = torch.empty((3, C), dtype=torch.int32, device=dev)
             d[H_LOSS] = loss.data_ptr()
         if want_logits:
-            logits = torch.empty((adjs[-1].shape[0], C), dtype=torch.float32, device=dev)
+            logits = torch.empty((self._rows(x0, adjs)[-1], C), dtype=torch.float32, device=dev)
         L = _lib.lib()
         wsb = L.gnn_eval_step_workspace_bytes(d.ctypes.data)
         if wsb == 0:
@@ -269,6 +287,16 @@ class NativeStep:
             _lib.check(L.gnn_eval_step_f32(d.ctypes.data, _p(logits), C, _p(counts), int(mode), ws.data_ptr(), wsb,
                                            _lib.stream_of(dev)), "gnn_eval_step_f32")
         return loss, counts, logits
+
+    @staticmethod
+    def _rows(x0, adjs):
+        """Every layer's output rows M: the operand's, or for an order-0 layer (no operand) its
+        input's: x0's rows at layer 0, else the layer below's M."""
+        rows, m = [], x0.shape[0]
+        for op in adjs:
+            m = m if op is None else op.shape[0]
+            rows.append(m)
+        return rows
 
     def _desc(self, x0, adjs, sampled_nodes, labels, seeds: bool, forward_only: bool = False):
         model = self.model
@@ -286,6 +314,10 @@ class NativeStep:
         sv = torch.randint(0, 2**62, (len(adjs) + 1,)).tolist() if (tr and seeds) else None
         for li, op in enumerate(adjs):
             b = HEADER + li * LAYER_SLOTS
+            d[b + L_SEED] = sv[li] if sv is not None else 0
+            if op is None:  # order 0 (GNN_SL_DENSE): no operand, M = K = the input's rows
+                d[b + L_M] = d[b + L_K] = self._rows(x0, adjs)[li]
+                continue
             d[b + L_ROWPTR], d[b + L_COL], d[b + L_VAL] = op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr()
             d[b + L_M], d[b + L_K], d[b + L_NNZ] = op.shape[0], op.shape[1], op.nnz
             if li >= 1 and not forward_only:
@@ -296,14 +328,14 @@ class NativeStep:
                 d[b + L_SAMPLED], d[b + L_NSAMPLED] = s.data_ptr(), s.numel()
                 r = getattr(s, "_gnn_rmap", None)
                 d[b + L_RMAP] = _p(r) if li >= 1 else 0
-            d[b + L_SEED] = sv[li] if sv is not None else 0
         d[H_HEAD_SEED] = sv[len(adjs)] if sv is not None else 0
         return d
 
     @staticmethod
     def _arm_timing(d, nl):
         """custom_sparse_ops timing is on (bench roofline): one event pair per aggregation launch
-        (nl forwards + nl - 1 backwards), armed by the executor around its SpMM kernels."""
+        (at most nl forwards + nl - 1 backwards; order-0 layers have none), armed by the executor
+        around its SpMM kernels."""
         n = 2 * nl - 1
         T = np.zeros(1 + TIMING_SLOTS * n, dtype=np.int64)
         T[0] = n

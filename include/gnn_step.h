@@ -58,6 +58,29 @@
  *     xs buffer (gnn_gather_rows_h16_f32) for linearB and its weight gradient: the split3 GEMMs do
  *     not read 16-bit rows in place. Any other value, or a non-zero kind on a layer >= 1, is
  *     refused like a bad loss kind: both *_workspace_bytes functions return 0, nothing is launched.
+ *     GNN_SL_DENSE: 0 = an aggregating layer (every descriptor built before the slot had a meaning,
+ *     so GNN_STEP_VERSION stays 1); 1 = an order-0 layer (the reference's --orders 0, models.py:17-21,
+ *     59-60): Y_l = sage_norm(X·W_Wᵀ + b_W). Any other value is refused like a bad loss kind (both
+ *     *_workspace_bytes functions return 0, nothing is launched, gnn_last_error() names the layer).
+ *     An order-0 layer has no operand: ROWPTR / COL / VAL / NNZ / T* / SAMPLED / NSAMPLED / RMAP are
+ *     ignored and may be 0. K must equal M; for l >= 1 that is M_{l-1}, for l = 0 the row count of x0.
+ *     SAGE: linearB takes no part, so WB / BB / GWB / GBB are ignored and may be 0 (never written),
+ *     and the layer's output is N wide, not 2N: scale / offset have N entries, the layer above reads
+ *     F_{l+1} = N and the head D = D_top. GCN: N wide as every layer. All layers may be order 0 (an
+ *     MLP). Forward: X is read in place (x0 at ldx0, or the layer below's output), one product routed
+ *     as the aggregating layers' pairs (split3 where its tiles fill the chip, else rocBLAS), then the
+ *     tail. Backward: for l >= 1 the input gradient dhW·W_W is written straight into layer l-1's
+ *     gradient buffer (no transpose, no aggregation); the weight gradient dhWᵀ·X reads X in place.
+ *     An aggregating layer above an order-0 layer may still have its backward aggregation folded
+ *     into that layer's tail backward; results are bit-identical either way. With GNN_SL_XKIND 16-bit
+ *     on an order-0 layer 0 the rows are widened once into the workspace (gnn_gather_rows_h16_f32,
+ *     exact) and the layer runs as fp32: bit-identical to the step on the widened x0.
+ *     Phases: with an order-0 layer 0 a phase-1 call launches no kernel (it still records the
+ *     staging gate if GNN_SH_STAGE_LAYER is 0) and phase 2 issues what phase 0 does; 1 + 2 equals 0
+ *     for every mix of orders. The staging gate is recorded exactly once per step: right after layer
+ *     GNN_SH_STAGE_LAYER's forward aggregation, or, if that layer is order 0, where the aggregation
+ *     would have been issued — before the layer's GEMM. Timing records are written for aggregations
+ *     only; the NSAMPLED == M check applies to aggregating SAGE layers only.
  */
 #ifndef GNN_STEP_H
 #define GNN_STEP_H
@@ -91,7 +114,7 @@ enum {
   GNN_SL_TROWPTR = 6, GNN_SL_TCOL = 7, GNN_SL_TVAL = 8, GNN_SL_SAMPLED = 9, GNN_SL_NSAMPLED = 10,
   GNN_SL_RMAP = 11, GNN_SL_WW = 12, GNN_SL_BW = 13, GNN_SL_WB = 14, GNN_SL_BB = 15, GNN_SL_SCALE = 16,
   GNN_SL_OFFSET = 17, GNN_SL_GWW = 18, GNN_SL_GBW = 19, GNN_SL_GWB = 20, GNN_SL_GBB = 21, GNN_SL_GSCALE = 22,
-  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24, GNN_SL_XKIND = 25
+  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24, GNN_SL_XKIND = 25, GNN_SL_DENSE = 26
 };
 
 size_t gnn_train_step_workspace_bytes(const int64_t* desc);
