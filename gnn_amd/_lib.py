@@ -91,6 +91,7 @@ _SIGNATURES = {
                                     ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gnn_head_bce_bwd_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, ctypes.c_float,
                                     ctypes.c_uint64, _INT, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "gnn_head_bias_grad_f32": (_INT, [_VP, _I64, _I64, _VP, _VP]),
     "gnn_head_eval_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _INT,
                                  _VP]),
     "gnn_head_ce_fwd_f32": (_INT, [_VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _I64, ctypes.c_float,
@@ -120,6 +121,12 @@ _SIGNATURES = {
                                            _I64, _VP, _I64, _VP, _SZ, _VP]),
     "gnn_gemm_f32_split3": (_INT, [_INT, _INT, _I64, _I64, _I64, _INT, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _SZ,
                                    _VP]),
+    # the split kernel at 1-3 pieces (the reduced-precision modes): the split3 arguments after `pieces`
+    "gnn_gemm_f32_split_workspace_bytes": (_SZ, [_INT, _I64, _I64, _I64, _INT]),
+    "gnn_gemm_f32_split": (_INT, [_INT, _INT, _INT, _I64, _I64, _I64, _INT, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _SZ,
+                                  _VP]),
+    "gnn_gemm_f32_split_indexed": (_INT, [_INT, _INT, _INT, _I64, _I64, _I64, _INT, _VP, _I64, _VP, _I64, _VP, _I64,
+                                          _VP, _I64, _VP, _I64, _VP, _SZ, _VP]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

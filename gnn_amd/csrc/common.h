@@ -27,18 +27,21 @@ bool spmm_row_chain(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, i
 
 // gnn_gemm_f32_split3 with the split-k and tail-tile choices made for a batch of split_nbatch
 // products (gemm.hip): product batch_index of that batch launched on its own (nbatch = 1),
-// bit-identical to its result in the batched launch.
+// bit-identical to its result in the batched launch. pieces: as gnn_gemm_f32_split (3: split3).
 int gemm_split3_as_batch(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch, int split_nbatch,
                          int batch_index, const float* const* A, int64_t lda, const float* const* B, int64_t ldb,
-                         float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream);
+                         float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream,
+                         int pieces = 3);
 
 // gnn_gemm_f32_split3 with row-indexed operands: A's row m is A[ia[b][m]] (m-major A, a_rows
 // source rows), B's row k is B[ib[b][k]] (k-major B, b_rows source rows); NULL arrays / entries:
-// not indexed. Same sums as the split3 product of the gathered operands (gemm.hip).
+// not indexed. Same sums as the split3 product of the gathered operands (gemm.hip). pieces: as
+// gnn_gemm_f32_split (3: split3).
 int gemm_split3_indexed(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
                         const float* const* A, int64_t lda, const int64_t* const* ia, int64_t a_rows,
                         const float* const* B, int64_t ldb, const int64_t* const* ib, int64_t b_rows,
-                        float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream);
+                        float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream,
+                        int pieces = 3);
 
 }  // namespace gnn
 

@@ -395,9 +395,45 @@ __device__ __forceinline__ int s3_chunk(int row, int h) {
   else return (2 * row + (h ^ ((row >> 3) & 1))) * 8;
 }
 
-// Split 8 floats into their three bf16 pieces (by truncation, x = h + m + l exactly), two
-// elements packed per word.
+typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
+
+// Two floats rounded to bf16 (round to nearest even: v_cvt_pk_bf16_f32), a in the low half.
+__device__ __forceinline__ unsigned int rne_pk(float a, float b) {
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f2{a, b}, bf2v));
+}
+
+// Split 8 floats into their NP bf16 pieces, two elements packed per word.
+//  * NP = 3: by truncation, x = h + m + l exactly.
+//  * NP = 2 ("split2"): x is replaced by x' = h + RNE_bf16(x - h), h as above (|x - x'| <= 2^-15 |x|),
+//    and the two pieces are split3's h and m of x' (its l is 0).
+//  * NP = 1 ("bf16"): h = RNE_bf16(x).
+// The last kept piece is rounded to nearest even (v_cvt_pk_bf16_f32); an operand that already fits
+// NP pieces splits into split3's pieces with zeros below. Pieces past NP are not written.
+template <int NP = 3>
 __device__ __forceinline__ void split8(const float v[8], u4v& ph, u4v& pm, u4v& pl) {
+  if constexpr (NP == 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph[j] = rne_pk(v[2 * j], v[2 * j + 1]);
+    return;
+  } else if constexpr (NP == 2) {
+    // The pieces are split3's pieces of x' = h + RNE_bf16(x - h), so that the products sum exactly
+    // as split3 sums them on x'. They are (h, RNE_bf16(x - h)) unless the remainder rounds up to
+    // one unit of h's last place — its low 16 bits are 0xff80 or above — where x' = h + ulp splits
+    // as (h + ulp, 0). Adding 0x80 to the bits carries into the high half exactly then; the
+    // remainder against that h is negative there (else x - h itself), and the median with 0 and x
+    // makes it 0.
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = v[2 * j], x1 = v[2 * j + 1];
+      const unsigned int h0 = (__float_as_uint(x0) + 0x80u) & 0xffff0000u;
+      const unsigned int h1 = (__float_as_uint(x1) + 0x80u) & 0xffff0000u;
+      const float r0 = __builtin_amdgcn_fmed3f(x0 - __uint_as_float(h0), 0.0f, x0);  // the subtraction is exact
+      const float r1 = __builtin_amdgcn_fmed3f(x1 - __uint_as_float(h1), 0.0f, x1);
+      ph[j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
+      pm[j] = rne_pk(r0, r1);
+    }
+    return;
+  }
   // per pair of elements: 4 v_and, 4 v_sub_f32 and 3 v_perm (one per piece, packing the two high
   // halves). The kernel is bound by the SIMD's issue port (VALU + MFMA issue); the subtractions
   // stay scalar: the packed form (v_pk_add_f32, two elements per instruction) measured 2-5 %
@@ -417,21 +453,21 @@ __device__ __forceinline__ void split8(const float v[8], u4v& ph, u4v& pm, u4v& 
   }
 }
 
-// 8 floats of (image row rr, k half kh) split into the stage's three piece images, each R x 16 bf16.
-template <bool KMAJ, int R>
+// 8 floats of (image row rr, k half kh) split into the stage's NP piece images, each R x 16 bf16.
+template <bool KMAJ, int R, int NP = 3>
 __device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int rr, int kh, const float v[8]) {
   u4v ph, pm, pl;
-  split8(v, ph, pm, pl);
+  split8<NP>(v, ph, pm, pl);
   const int off = s3_chunk<KMAJ, R>(rr, kh);
   *reinterpret_cast<u4v*>(S + off) = ph;
-  *reinterpret_cast<u4v*>(S + R * S3_BK + off) = pm;
-  *reinterpret_cast<u4v*>(S + 2 * R * S3_BK + off) = pl;
+  if constexpr (NP >= 2) *reinterpret_cast<u4v*>(S + R * S3_BK + off) = pm;
+  if constexpr (NP >= 3) *reinterpret_cast<u4v*>(S + 2 * R * S3_BK + off) = pl;
 }
 
 // The thread's own 8 floats of a 128-row operand tile (row and k half as s3_load deals them).
-template <bool KMAJ, int R>
+template <bool KMAJ, int R, int NP = 3>
 __device__ __forceinline__ void s3_store(unsigned short* __restrict__ S, int t, const float v[8]) {
-  s3_store<KMAJ, R>(S, KMAJ ? (t & 127) : (t >> 1), KMAJ ? (t >> 7) : (t & 1), v);
+  s3_store<KMAJ, R, NP>(S, KMAJ ? (t & 127) : (t >> 1), KMAJ ? (t >> 7) : (t & 1), v);
 }
 
 template <bool KMAJ, int R>
@@ -439,16 +475,30 @@ __device__ __forceinline__ bf8v s3_frag(const unsigned short* __restrict__ S, in
   return __builtin_bit_cast(bf8v, *reinterpret_cast<const u4v*>(S + piece * R * S3_BK + s3_chunk<KMAJ, R>(row, h)));
 }
 
-// The six piece products of one k16 step into the wave's 2 x NB accumulators (small terms first;
-// per B block its three pieces, then the six products: the same order per output at every NB).
+// The piece products (A piece, B piece; 0 = h, 1 = m, 2 = l) of one k16 step at NP pieces, in
+// accumulation order: split3's six, and that list without the products of a dropped piece.
+constexpr int s3_products(int np) { return np == 3 ? 6 : np == 2 ? 4 : 1; }
+constexpr int s3_piece_a(int np, int q) {
+  constexpr int P3[6] = {2, 1, 0, 1, 0, 0}, P2[4] = {1, 1, 0, 0};
+  return np == 3 ? P3[q] : np == 2 ? P2[q] : 0;
+}
+constexpr int s3_piece_b(int np, int q) {
+  constexpr int P3[6] = {0, 1, 2, 0, 1, 0}, P2[4] = {1, 0, 1, 0};
+  return np == 3 ? P3[q] : np == 2 ? P2[q] : 0;
+}
+
+// The piece products of one k16 step into the wave's 2 x NB accumulators (small terms first;
+// per B block its pieces, then the products: the same order per output at every NB).
+// NP = 3: the six products l·h, m·m, h·l, m·h, h·m, h·h; NP = 2: that list without the two l
+// products (m·m, m·h, h·m, h·h: the exact product of the rounded operands); NP = 1: h·h.
 // The A image has 128 rows, the B image the tile's 64 NB.
-template <bool AK, bool BKM, int NB>
+template <bool AK, bool BKM, int NB, int NP = 3>
 __device__ __forceinline__ void s3_mma(const unsigned short* __restrict__ Sa, const unsigned short* __restrict__ Sb,
                                        int ra0, int rb0, int li, int lh, f16v (&acc)[2][NB]) {
   constexpr int G = NB == 2 ? 2 : 1;  // B blocks whose pieces are held at once (NB = 4 has no registers for two)
-  bf8v a[2][3], bb[G][3];
+  bf8v a[2][NP], bb[G][NP];
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
+  for (int p = 0; p < NP; ++p)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       a[i][p] = s3_frag<AK, BM>(Sa, p, ra0 + i * 32 + li, lh);
@@ -458,18 +508,17 @@ __device__ __forceinline__ void s3_mma(const unsigned short* __restrict__ Sa, co
   for (int j0 = 0; j0 < NB; j0 += G) {
     if constexpr (G == 1) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p) bb[0][p] = s3_frag<BKM, 64 * NB>(Sb, p, rb0 + j0 * 32 + li, lh);
+      for (int p = 0; p < NP; ++p) bb[0][p] = s3_frag<BKM, 64 * NB>(Sb, p, rb0 + j0 * 32 + li, lh);
     }
-    constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-    constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
+    // the products whose pieces are both kept, in split3's order (piece 0 = h, 1 = m, 2 = l)
 #pragma unroll
-    for (int q = 0; q < 6; ++q)
+    for (int q = 0; q < s3_products(NP); ++q)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int g = 0; g < G; ++g)
-          acc[i][j0 + g] =
-              __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], bb[g][PB[q]], acc[i][j0 + g], 0, 0, 0);
+          acc[i][j0 + g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][s3_piece_a(NP, q)], bb[g][s3_piece_b(NP, q)],
+                                                                  acc[i][j0 + g], 0, 0, 0);
   }
 }
 
@@ -498,15 +547,22 @@ __device__ __forceinline__ int3 xcd_tile(int gx, int gy, unsigned gz, unsigned b
 // and every output element accumulates the same pieces in the same order at either width (per k16
 // step the six products h·h .. l·h, small terms first): whole tiles are bit-identical.
 // Tail-tile mode (tail_s > 0, see tail_plan) is NB = 2 only.
-template <bool AK, bool BKM, int VA, int VB, bool IDX, int NB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 2 ? 3 : 2, NB == 2 ? 3 : 2))) void
+// NP: bf16 pieces per operand (3: split3; 2, 1: the reduced modes "split2" / "bf16" of
+// gnn_gemm_f32_split, NB = 2 only). The tile, the k steps, the pipeline and the plan are split3's;
+// a reduced mode splits into NP pieces (the last one rounded to nearest even), keeps NP piece
+// images per operand and stage (LDS 32 / 16 KB per workgroup: a fourth workgroup per CU where
+// the registers allow it) and issues the 4 / 1 products of the kept pieces, in split3's order.
+template <bool AK, bool BKM, int VA, int VB, bool IDX, int NB, int NP = 3>
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(NB == 2 ? 3 : 2, NB == 2 ? (NP == 3 ? 3 : 4) : 2))) void
 gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int splits, int klen,
                float* __restrict__ part, int64_t abytes, int64_t bbytes, int xcd_map, int tail_base = 0,
                int tail_s = 0) {
   constexpr int TN = 64 * NB;  // tile width = rows of the B images
   constexpr int NH = NB / 2;   // 128-row halves of the B tile
-  __shared__ __attribute__((aligned(16))) unsigned short As[2][S3_OPER];
-  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * S3_OPER];
+  static_assert(NP >= 1 && NP <= 3 && (NP == 3 || NB == 2), "reduced piece counts: the 128 x 128 tile only");
+  __shared__ __attribute__((aligned(16))) unsigned short As[2][NP * S3_PIECE];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][NH * NP * S3_PIECE];
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wid = t >> 6;
@@ -589,12 +645,12 @@ gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t 
   };
   auto store_ab = [&](int stage, const float(&xa)[8], const float(&xb)[8 * NH]) {
     if constexpr (NH == 2) {
-      s3_store<AK, BM>(As[stage], ar, ah, xa);
-      s3_store<BKM, TN>(Bs[stage], br, bh, xb);
-      s3_store<BKM, TN>(Bs[stage], br + BN, bh, xb + 8);
+      s3_store<AK, BM, NP>(As[stage], ar, ah, xa);
+      s3_store<BKM, TN, NP>(Bs[stage], br, bh, xb);
+      s3_store<BKM, TN, NP>(Bs[stage], br + BN, bh, xb + 8);
     } else {
-      s3_store<AK, BM>(As[stage], t, xa);
-      s3_store<BKM, TN>(Bs[stage], t, xb);
+      s3_store<AK, BM, NP>(As[stage], t, xa);
+      s3_store<BKM, TN, NP>(Bs[stage], t, xb);
     }
   };
   const int li = lane & 31, lh = lane >> 5;
@@ -607,17 +663,17 @@ gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t 
     for (; kt + 1 < nfull; kt += 2) {
       // tile kt from stage 0; tile kt+1 (set 1) -> stage 1; set 0 <- tile kt+2
       load_ab(kt + 2, ra[0], rb[0]);
-      s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
+      s3_mma<AK, BKM, NB, NP>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
       store_ab(1, ra[1], rb[1]);
       __syncthreads();
       // tile kt+1 from stage 1; tile kt+2 (set 0) -> stage 0; set 1 <- tile kt+3
       load_ab(kt + 3, ra[1], rb[1]);
-      s3_mma<AK, BKM, NB>(As[1], Bs[1], wm * 64, wn * (32 * NB), li, lh, acc);
+      s3_mma<AK, BKM, NB, NP>(As[1], Bs[1], wm * 64, wn * (32 * NB), li, lh, acc);
       store_ab(0, ra[0], rb[0]);
       __syncthreads();
     }
     if (nfull & 1) {  // odd count: the last full tile is in stage 0
-      s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
+      s3_mma<AK, BKM, NB, NP>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
       __syncthreads();
     }
   }
@@ -639,7 +695,7 @@ gemm_s3_kernel(Batch bt, int M, int N, int K, int64_t lda, int64_t ldb, int64_t 
     }
     store_ab(0, ra[0], rb[0]);
     __syncthreads();
-    s3_mma<AK, BKM, NB>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
+    s3_mma<AK, BKM, NB, NP>(As[0], Bs[0], wm * 64, wn * (32 * NB), li, lh, acc);
   }
 
   if constexpr (NB == 2) {
@@ -922,10 +978,13 @@ struct Plan {
   }
 };
 
-Plan plan_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch, int split_nbatch = 0, int batch_index = -1) {
+// pieces: the split kernel's piece count; the reduced modes (< 3) take split3's NB = 2 plan
+// whatever GNN_GEMM_WIDE says (the wide tile has no reduced form).
+Plan plan_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch, int split_nbatch = 0, int batch_index = -1,
+             int pieces = 3) {
   const int nb = split_nbatch > 0 ? split_nbatch : nbatch;
   Plan p;
-  p.kern = algo != ALGO_S3 ? KERN_F32 : use_wide(M, N, K, nb) ? KERN_S3W : KERN_S3;
+  p.kern = algo != ALGO_S3 ? KERN_F32 : (pieces == 3 && use_wide(M, N, K, nb)) ? KERN_S3W : KERN_S3;
   if (K > 0)
     p.splits = p.kern == KERN_S3W   ? pick_splits(M, N, K, nb, W_BN, SLOTS_S3W)
                : p.kern == KERN_S3 ? pick_splits(M, N, K, nb, BN, SLOTS_S3)
@@ -948,9 +1007,9 @@ Plan plan_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch, int split_nb
   return p;
 }
 
-size_t workspace_bytes_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch) {
+size_t workspace_bytes_of(int algo, int64_t M, int64_t N, int64_t K, int nbatch, int pieces = 3) {
   if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return 0;
-  return plan_of(algo, M, N, K, nbatch).bytes(M, N, nbatch);
+  return plan_of(algo, M, N, K, nbatch, 0, -1, pieces).bytes(M, N, nbatch);
 }
 
 // C[b] = the split-k slabs summed in split order (bt: C only).
@@ -975,6 +1034,7 @@ int launch_splitk_reduce(const Batch& bt, const float* part, int64_t M, int64_t 
 struct Launch {
   Kern kern;
   bool idx;  // split3: some operand carries a row index
+  int np;    // split3: pieces per operand (3; 2 / 1: the reduced modes, KERN_S3 only)
   int bkt;   // f32 kernel: k depth of a stage
   dim3 grid;
   hipStream_t st;
@@ -987,11 +1047,28 @@ struct Launch {
   int xcdm, tail_base, tail_s;
 };
 
+// The split kernel at a reduced piece count (NB = 2).
+template <bool AK, bool BKM, int VA, int VB, int NP>
+void launch_s3_reduced(const Launch& l) {
+  auto k = gemm_s3_kernel<AK, BKM, VA, VB, false, 2, NP>;
+  if constexpr (!AK || BKM)
+    if (l.idx) k = gemm_s3_kernel<AK, BKM, VA, VB, true, 2, NP>;
+  k<<<l.grid, dim3(256), 0, l.st>>>(l.bt, l.M, l.N, l.K, l.lda, l.ldb, l.ldc, l.splits, l.klen, l.part, l.abytes,
+                                    l.bbytes, l.xcdm, l.tail_base, l.tail_s);
+}
+
 template <bool AK, bool BKM, int VA, int VB>
 void launch_gemm(const Launch& l) {
   if (l.kern == KERN_F32) {
     auto k = l.bkt == 16 ? gemm_f32_kernel<AK, BKM, VA, VB, 16> : gemm_f32_kernel<AK, BKM, VA, VB, 32>;
     k<<<l.grid, dim3(256), 0, l.st>>>(l.bt, l.M, l.N, l.K, l.lda, l.ldb, l.ldc, l.splits, l.klen, l.part);
+    return;
+  }
+  if (l.np < 3) {
+    // a k-major operand is read by 4-byte loads at either width: one instantiation for both
+    constexpr int CVA = AK ? 4 : VA, CVB = BKM ? 4 : VB;
+    if (l.np == 2) launch_s3_reduced<AK, BKM, CVA, CVB, 2>(l);
+    else launch_s3_reduced<AK, BKM, CVA, CVB, 1>(l);
     return;
   }
   const bool wide = l.kern == KERN_S3W;
@@ -1021,11 +1098,13 @@ struct RowIndex {
   int64_t b_rows = 0;
 };
 
-// split_nbatch, batch_index: see plan_of.
+// split_nbatch, batch_index, pieces: see plan_of.
 int gemm_run(int algo, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch, const float* const* A,
              int64_t lda, const float* const* B, int64_t ldb, float* const* C, int64_t ldc, void* workspace,
              size_t workspace_bytes, void* stream, int split_nbatch = 0, const RowIndex* ri = nullptr,
-             int batch_index = -1) {
+             int batch_index = -1, int pieces = 3) {
+  GNN_REQUIRE(pieces >= 1 && pieces <= 3 && (pieces == 3 || algo == ALGO_S3),
+              "gnn_gemm_f32_split: pieces %d (1: bf16, 2: split2, 3: split3)", pieces);
   GNN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gnn_gemm_f32: negative size");
   GNN_REQUIRE(M < INT_MAX && N < INT_MAX && K < INT_MAX, "gnn_gemm_f32: sizes must be < 2^31");
   GNN_REQUIRE(nbatch >= 1 && nbatch <= MAX_BATCH, "gnn_gemm_f32: nbatch must be 1..%d", MAX_BATCH);
@@ -1058,9 +1137,11 @@ int gemm_run(int algo, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t
   l.bbytes = K == 0 ? 0 : (brows - 1) * ldb * 4 + (b_kmajor ? N : K) * 4;
   if (algo == ALGO_S3 && (l.abytes >= INT_MAX || l.bbytes >= INT_MAX)) {
     GNN_REQUIRE(!l.idx, "gnn_gemm: indexed operand of >= 2 GiB");
+    GNN_REQUIRE(pieces == 3, "gnn_gemm_f32_split: operand of >= 2 GiB at %d pieces", pieces);
     algo = ALGO_F32;
   }
-  Plan pl = plan_of(algo, M, N, K, nbatch, split_nbatch, batch_index);
+  l.np = pieces;
+  Plan pl = plan_of(algo, M, N, K, nbatch, split_nbatch, batch_index, pieces);
   if (!tail_enabled()) pl.tp = TailPlan{};
   const TailPlan& tp = pl.tp;
   l.kern = pl.kern;
@@ -1200,28 +1281,53 @@ int gnn_gemm_f32_split3_indexed(int a_kmajor, int b_kmajor, int64_t M, int64_t N
                                   workspace, workspace_bytes, stream);
 }
 
+size_t gnn_gemm_f32_split_workspace_bytes(int pieces, int64_t M, int64_t N, int64_t K, int nbatch) {
+  if (pieces < 1 || pieces > 3) return 0;
+  return workspace_bytes_of(ALGO_S3, M, N, K, nbatch, pieces);
+}
+
+int gnn_gemm_f32_split(int pieces, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
+                       const float* const* A, int64_t lda, const float* const* B, int64_t ldb, float* const* C,
+                       int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
+  return gemm_run(ALGO_S3, a_kmajor, b_kmajor, M, N, K, nbatch, A, lda, B, ldb, C, ldc, workspace, workspace_bytes,
+                  stream, 0, nullptr, -1, pieces);
+}
+
+int gnn_gemm_f32_split_indexed(int pieces, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
+                               const float* const* A, int64_t lda, const int64_t* const* ia, int64_t a_rows,
+                               const float* const* B, int64_t ldb, const int64_t* const* ib, int64_t b_rows,
+                               float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
+  GNN_REQUIRE(pieces >= 1 && pieces <= 3, "gnn_gemm_f32_split_indexed: pieces %d (1: bf16, 2: split2, 3: split3)",
+              pieces);
+  GNN_REQUIRE((!ia || a_rows > 0) && (!ib || b_rows > 0), "gnn_gemm_f32_split_indexed: source rows");
+  return gnn::gemm_split3_indexed(a_kmajor, b_kmajor, M, N, K, nbatch, A, lda, ia, a_rows, B, ldb, ib, b_rows, C, ldc,
+                                  workspace, workspace_bytes, stream, pieces);
+}
+
 }  // extern "C"
 
 namespace gnn {
 
 int gemm_split3_as_batch(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch, int split_nbatch,
                          int batch_index, const float* const* A, int64_t lda, const float* const* B, int64_t ldb,
-                         float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
+                         float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream,
+                         int pieces) {
   return gemm_run(ALGO_S3, a_kmajor, b_kmajor, M, N, K, nbatch, A, lda, B, ldb, C, ldc, workspace, workspace_bytes,
-                  stream, split_nbatch, nullptr, batch_index);
+                  stream, split_nbatch, nullptr, batch_index, pieces);
 }
 
 int gemm_split3_indexed(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
                         const float* const* A, int64_t lda, const int64_t* const* ia, int64_t a_rows,
                         const float* const* B, int64_t ldb, const int64_t* const* ib, int64_t b_rows,
-                        float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
+                        float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream,
+                        int pieces) {
   RowIndex ri;
   ri.ia = ia;
   ri.a_rows = a_rows;
   ri.ib = ib;
   ri.b_rows = b_rows;
   return gemm_run(ALGO_S3, a_kmajor, b_kmajor, M, N, K, nbatch, A, lda, B, ldb, C, ldc, workspace, workspace_bytes,
-                  stream, 0, &ri);
+                  stream, 0, &ri, -1, pieces);
 }
 
 }  // namespace gnn

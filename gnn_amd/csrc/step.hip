@@ -178,14 +178,29 @@ bool f32_gemm() {
   return e && std::string(e) == "f32";
 }
 
-int gemm(int ak, int bk, int64_t M, int64_t N, int64_t K, int nb, const float* const* A, int64_t lda,
-         const float* const* B, int64_t ldb, float* const* C, int64_t ldc, void* ws, size_t wsb, hipStream_t st) {
-  if (f32_gemm()) return gnn_gemm_f32(ak, bk, M, N, K, nb, A, lda, B, ldb, C, ldc, ws, wsb, st);
-  return gnn_gemm_f32_split3(ak, bk, M, N, K, nb, A, lda, B, ldb, C, ldc, ws, wsb, st);
+// The split kernel's piece count for a layer whose GNN_SL_GEMM slot is np: the slot's, or for 0 what
+// GNN_GEMM_ALGO says (split2: 2, bf16: 1 — the reduced-precision modes of gnn_gemm_f32_split,
+// process-wide; anything else: split3). Read per call, as f32_gemm().
+int pieces_of(int np) {
+  if (np) return np;
+  const char* e = getenv("GNN_GEMM_ALGO");
+  if (!e) return 3;
+  const std::string a(e);
+  return a == "split2" ? 2 : a == "bf16" ? 1 : 3;
 }
 
+// np: the layer's GNN_SL_GEMM slot (0: GNN_GEMM_ALGO decides, f32 included)
+int gemm(int np, int ak, int bk, int64_t M, int64_t N, int64_t K, int nb, const float* const* A, int64_t lda,
+         const float* const* B, int64_t ldb, float* const* C, int64_t ldc, void* ws, size_t wsb, hipStream_t st) {
+  if (np == 0 && f32_gemm()) return gnn_gemm_f32(ak, bk, M, N, K, nb, A, lda, B, ldb, C, ldc, ws, wsb, st);
+  return gnn_gemm_f32_split(pieces_of(np), ak, bk, M, N, K, nb, A, lda, B, ldb, C, ldc, ws, wsb, st);
+}
+
+// (the reduced piece counts plan as split3 at its 128 x 128 tile: the same bytes unless
+// GNN_GEMM_WIDE moves split3 itself to the wide tile)
 size_t gemm_ws(int64_t M, int64_t N, int64_t K, int nb) {
-  return std::max(gnn_gemm_f32_split3_workspace_bytes(M, N, K, nb), gnn_gemm_f32_workspace_bytes(M, N, K, nb));
+  return std::max({gnn_gemm_f32_split3_workspace_bytes(M, N, K, nb), gnn_gemm_f32_workspace_bytes(M, N, K, nb),
+                   gnn_gemm_f32_split_workspace_bytes(2, M, N, K, nb)});
 }
 
 // GNN_STEP_OVERLAP=1 turns the aux stream on. Off by default: measured on the Reddit config-2
@@ -246,6 +261,7 @@ struct LayerBufs {
   // place (a 16-bit X0 widened once into feat, rows of ldo floats), and the input gradient dhW·W_W
   // is written straight into the layer below's dY
   bool dense;
+  int np;  // GNN_SL_GEMM: pieces of the layer's split-kernel products (0: GNN_GEMM_ALGO, see pieces_of)
   const float* X;
   // layer 0 over a 16-bit X0 (GNN_SL_XKIND = GNN_FEAT_F16 / GNN_FEAT_BF16): X is NULL, X16 the rows
   // (ldx in elements); the aggregation reads them as they are and x[sampled] is widened into xs
@@ -304,6 +320,11 @@ int shapes(const int64_t* d, bool measuring, Plan& pl) {
     GNN_REQUIRE(dense == 0 || dense == 1, "gnn_train_step: layer %d dense flag %lld (0: aggregating, 1: order 0)", l,
                 (long long)dense);
     b.dense = dense != 0;
+    const int64_t np = L(d, l, GNN_SL_GEMM);
+    GNN_REQUIRE(np >= 0 && np <= 3,
+                "gnn_train_step: layer %d GEMM pieces %lld (0: GNN_GEMM_ALGO, 1: bf16, 2: split2, 3: split3)", l,
+                (long long)np);
+    b.np = (int)np;
     b.D = b.dense ? N : n * N;
     if (b.dense) {
       GNN_REQUIRE(b.K == b.M, "gnn_train_step: order-0 layer %d has K = %lld, M = %lld", l, (long long)b.K,
@@ -566,7 +587,7 @@ int forward(Run& r) {
         const float* A[1] = {X};
         const float* B[1] = {WW};
         float* Cc[1] = {b.hW};
-        GNN_TRY(gemm(0, 0, b.M, N, b.F, 1, A, ldx, B, b.F, Cc, N, b.ws_gemm_f, b.b_gemm_f, st));
+        GNN_TRY(gemm(b.np, 0, 0, b.M, N, b.F, 1, A, ldx, B, b.F, Cc, N, b.ws_gemm_f, b.b_gemm_f, st));
       } else {
         GNN_TRY(mm_xwt(h, X, ldx, WW, b.F, b.hW, N, b.M, N, b.F));
       }
@@ -591,7 +612,7 @@ int forward(Run& r) {
       const float* Bb[1] = {WB};
       float* Cb[1] = {b.hB};
       GNN_TRY(gnn::gemm_split3_as_batch(0, 0, b.M, N, b.F, 1, 2, 0, Ab, b.ldo, Bb, b.F, Cb, N, b.ws_gemm_f2, b.b_gemm_f,
-                                        aux->s));
+                                        aux->s, pieces_of(b.np)));
       if (phase != 2 || l != 0) {
         GNN_TRY(r.aggregate(l));
         GNN_TRY(r.stage_gate(l));
@@ -599,7 +620,8 @@ int forward(Run& r) {
       const float* Aw[1] = {b.feat};
       const float* Bw[1] = {WW};
       float* Cw[1] = {b.hW};
-      GNN_TRY(gnn::gemm_split3_as_batch(0, 0, b.M, N, b.F, 1, 2, 1, Aw, b.ldo, Bw, b.F, Cw, N, b.ws_gemm_f, b.b_gemm_f, st));
+      GNN_TRY(gnn::gemm_split3_as_batch(0, 0, b.M, N, b.F, 1, 2, 1, Aw, b.ldo, Bw, b.F, Cw, N, b.ws_gemm_f, b.b_gemm_f, st,
+                                        pieces_of(b.np)));
       GNN_TRY(fork_join(aux, aux->s, st));
     } else if (small_side) {
       b.xs_gathered = true;
@@ -633,13 +655,13 @@ int forward(Run& r) {
       const float* B[2] = {WB, WW};
       float* Cc[2] = {b.hB, b.hW};
       GNN_TRY(gnn::gemm_split3_indexed(0, 0, b.M, N, b.F, n, A, b.ldo, IA, b.K, B, b.F, nullptr, 0, Cc, N,
-                                       b.ws_gemm_f, b.b_gemm_f, st));
+                                       b.ws_gemm_f, b.b_gemm_f, st, pieces_of(b.np)));
     } else if (ok && fills(b.M, N, n)) {
       const float* A[2] = {pl.sage ? b.xs : b.feat, b.feat};
       const float* B[2] = {pl.sage ? WB : WW, WW};
       float* Cc[2] = {pl.sage ? b.hB : b.hW, b.hW};
-      GNN_TRY(gemm(0, 0, b.M, N, b.F, n, A + (pl.sage ? 0 : 1), b.ldo, B + (pl.sage ? 0 : 1), b.F,
-                                  Cc + (pl.sage ? 0 : 1), N, b.ws_gemm_f, b.b_gemm_f, st));
+      GNN_TRY(gemm(b.np, 0, 0, b.M, N, b.F, n, A + (pl.sage ? 0 : 1), b.ldo, B + (pl.sage ? 0 : 1), b.F,
+                   Cc + (pl.sage ? 0 : 1), N, b.ws_gemm_f, b.b_gemm_f, st));
     } else {
       if (pl.sage) GNN_TRY(mm_xwt(h, b.xs, b.ldo, WB, b.F, b.hB, N, b.M, N, b.F));
       GNN_TRY(mm_xwt(h, b.feat, b.ldo, WW, b.F, b.hW, N, b.M, N, b.F));
@@ -663,6 +685,15 @@ int check_workspace(const void* workspace, size_t workspace_bytes, size_t need) 
 }  // namespace
 
 extern "C" {
+
+int gnn_head_bias_grad_f32(const float* dz, int64_t M, int64_t C, float* db, void* stream) {
+  GNN_REQUIRE(M >= 0 && C >= 0 && M < INT_MAX && C < INT_MAX, "gnn_head_bias_grad_f32: bad size");
+  if (C == 0) return 0;
+  GNN_REQUIRE(db && (M == 0 || dz), "gnn_head_bias_grad_f32: NULL pointer");
+  colsum_kernel<<<dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream>>>(dz, (int)M, (int)C, db);
+  GNN_LAUNCHED("colsum_kernel");
+  return 0;
+}
 
 size_t gnn_train_step_workspace_bytes(const int64_t* desc) {
   if (!desc) return 0;
@@ -787,7 +818,7 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
         if (okd && fills(b.M, b.F, 1)) {
           const float* B[1] = {WW};
           float* Cc[1] = {dYp};
-          GNN_TRY(gemm(0, 1, b.M, b.F, N, 1, Gd, N, B, b.F, Cc, b.F, b.ws_gemm_dx, b.b_gemm_dx, st));
+          GNN_TRY(gemm(b.np, 0, 1, b.M, b.F, N, 1, Gd, N, B, b.F, Cc, b.F, b.ws_gemm_dx, b.b_gemm_dx, st));
         } else {
           GNN_TRY(mm_gw(h, b.dhW, N, WW, b.F, dYp, b.F, b.M, b.F, N));
         }
@@ -802,7 +833,7 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
         }
         const float* Xd[1] = {X};
         float* Cc[1] = {gWW};
-        GNN_TRY(gemm(1, 1, N, b.F, b.M, 1, Gd, N, Xd, ldx, Cc, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw));
+        GNN_TRY(gemm(b.np, 1, 1, N, b.F, b.M, 1, Gd, N, Xd, ldx, Cc, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw));
       } else {
         rocblas_handle hw = h;
         if (ha) {
@@ -824,8 +855,7 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
       if (ok && fills(b.M, b.F, n)) {
         const float* B[2] = {pl.sage ? WB : WW, WW};
         float* Cc[2] = {pl.sage ? b.dxs : b.dfeat, b.dfeat};
-        GNN_TRY(gemm(0, 1, b.M, b.F, N, n, G + o, N, B + o, b.F, Cc + o, b.F, b.ws_gemm_dx,
-                                    b.b_gemm_dx, st));
+        GNN_TRY(gemm(b.np, 0, 1, b.M, b.F, N, n, G + o, N, B + o, b.F, Cc + o, b.F, b.ws_gemm_dx, b.b_gemm_dx, st));
       } else {
         if (pl.sage) GNN_TRY(mm_gw(h, b.dhB, N, WB, b.F, b.dxs, b.F, b.M, b.F, N));
         GNN_TRY(mm_gw(h, b.dhW, N, WW, b.F, b.dfeat, b.F, b.M, b.F, N));
@@ -847,10 +877,9 @@ int gnn_train_step_f32(const int64_t* d, void* workspace, size_t workspace_bytes
       }
       if (pl.sage && !b.xs_gathered)
         GNN_TRY(gnn::gemm_split3_indexed(1, 1, N, b.F, b.M, n, G + o, N, nullptr, 0, X + o, b.ldo, IB + o, b.K,
-                                         Cc + o, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw));
+                                         Cc + o, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw, pieces_of(b.np)));
       else
-        GNN_TRY(gemm(1, 1, N, b.F, b.M, n, G + o, N, X + o, b.ldo, Cc + o, b.F, b.ws_gemm_dw,
-                                    b.b_gemm_dw, sw));
+        GNN_TRY(gemm(b.np, 1, 1, N, b.F, b.M, n, G + o, N, X + o, b.ldo, Cc + o, b.F, b.ws_gemm_dw, b.b_gemm_dw, sw));
       GNN_TRY(grads_ready(2 + l, sw));  // sw follows st's norm backward (fork_join)
     } else {
       // the small weight-gradient products (rocBLAS): on the aux stream beside the input gradients

@@ -30,7 +30,9 @@ LOSS_BCE, LOSS_CE = 0, 1
 TIMING_SLOTS = 16
 (L_ROWPTR, L_COL, L_VAL, L_M, L_K, L_NNZ, L_TROWPTR, L_TCOL, L_TVAL, L_SAMPLED, L_NSAMPLED, L_RMAP, L_WW, L_BW,
  L_WB, L_BB, L_SCALE, L_OFFSET, L_GWW, L_GBW, L_GWB, L_GBB, L_GSCALE, L_GOFFSET, L_SEED, L_XKIND,
- L_DENSE) = range(27)
+ L_DENSE, L_GEMM) = range(28)
+# GNN_SL_GEMM: bf16 pieces per operand of a layer's split-kernel products (0: GNN_GEMM_ALGO decides)
+GEMM_PIECES = {"split3": 3, "split2": 2, "bf16": 1}
 
 
 def _p(t: Optional[torch.Tensor]) -> int:
@@ -51,9 +53,13 @@ class NativeStep:
     gnn_eval_step_f32 for validation / test batches (main.py:178-199, 217-241): loss, per-class
     prediction counts and, on request, logits — the same parameters, no gradient touched.
     ``sigmoid_loss`` picks the loss of both (GNN_SH_LOSS_KIND): BCE with logits, or softmax
-    cross-entropy over the float label rows (utils.loss with sigmoid_loss=False)."""
+    cross-entropy over the float label rows (utils.loss with sigmoid_loss=False).
+    ``gemm`` picks the precision of the layers' matrix-core products (GNN_SL_GEMM; the training
+    step and ``evaluate`` alike): None leaves it to GNN_GEMM_ALGO (default split3, fp32-level
+    accuracy); "split3", or a reduced mode "split2" / "bf16" (fused.round_operand), or one such
+    name per layer, bottom-up. The routing, the vendor-GEMM products and the head do not change."""
 
-    def __init__(self, model, sigmoid_loss: bool = True):
+    def __init__(self, model, sigmoid_loss: bool = True, gemm=None):
         from . import models
 
         enc = model.encoder
@@ -68,6 +74,11 @@ class NativeStep:
         if any(g.order not in (0, 1) for g in enc.gcs) or not 1 <= len(enc.gcs) <= MAX_LAYERS:
             raise ValueError("NativeStep: every layer must have order 0 or 1 (1-4 layers)")
         self.dense = [g.order == 0 for g in enc.gcs]
+        names = [gemm] * len(enc.gcs) if (gemm is None or isinstance(gemm, str)) else list(gemm)
+        if len(names) != len(enc.gcs) or any(a is not None and a not in GEMM_PIECES for a in names):
+            raise ValueError(f"NativeStep: gemm must be None, one of {tuple(GEMM_PIECES)} or one such name per layer "
+                             f"({len(enc.gcs)}), got {gemm!r}")
+        self.gemm = names
         self.model = model
         self.enc = enc
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters()]
@@ -98,6 +109,7 @@ class NativeStep:
         for li, gc in enumerate(enc.gcs):
             b = HEADER + li * LAYER_SLOTS
             d[b + L_DENSE] = int(self.dense[li])
+            d[b + L_GEMM] = GEMM_PIECES[names[li]] if names[li] is not None else 0
             if self.kind == SAGE:
                 W, B = gc.linearW, gc.linearB
                 if not self.dense[li]:

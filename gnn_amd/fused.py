@@ -148,23 +148,56 @@ def _ld(t: torch.Tensor) -> int:
 
 
 GEMM_ALGOS = ("split3", "f32")
+# the opt-in reduced-precision modes of the split kernel (gnn_gemm_f32_split): fp32 operands and
+# fp32 accumulation, fewer mantissa bits on the matrix-core operands — see round_operand
+GEMM_REDUCED = ("split2", "bf16")
+# bf16 pieces per operand of the split kernel's modes
+GEMM_PIECES = {"split3": 3, "split2": 2, "bf16": 1}
 
 
 def gemm_algo() -> str:
     """The fp32 GEMM kernel (include/gnn_layers.h): "split3" (bf16 matrix cores on an exact
-    three-way split of every operand, six products, fp32 accumulation) or "f32" (f32-input
-    MFMA). GNN_GEMM_ALGO overrides the default."""
+    three-way split of every operand, six products, fp32 accumulation), "f32" (f32-input
+    MFMA), or a reduced mode of the split kernel: "split2" (two pieces, four products) or
+    "bf16" (one piece, one product). GNN_GEMM_ALGO overrides the default, split3."""
     a = os.environ.get("GNN_GEMM_ALGO", "split3")
-    if a not in GEMM_ALGOS:
-        raise RuntimeError(f"GNN_GEMM_ALGO must be one of {GEMM_ALGOS}, got {a!r}")
+    if a not in GEMM_ALGOS + GEMM_REDUCED:
+        raise RuntimeError(f"GNN_GEMM_ALGO must be one of {GEMM_ALGOS + GEMM_REDUCED}, got {a!r}")
     return a
 
 
+def _split_kernel(algo: str) -> bool:
+    """Whether the mode runs on the split kernel (split3 and its reduced modes route alike)."""
+    return algo in GEMM_PIECES
+
+
+def round_operand(t: torch.Tensor, algo: str) -> torch.Tensor:
+    """What a GEMM mode does to every fp32 operand element x before the exact bf16 x bf16
+    products are accumulated in fp32 — the definition of the reduced modes (CPU or GPU):
+      "bf16":   x' = RNE_bf16(x) (round to nearest even: x.bfloat16()), |x - x'| <= 2^-8 |x|;
+      "split2": h = trunc_bf16(x) (the top 8 significant bits), r = x - h (exact),
+                x' = h + RNE_bf16(r) (exact in fp32), |x - x'| <= 2^-15 |x|;
+      "split3" / "f32": x' = x (fp32-level accuracy).
+    Idempotent; the identity on operands of at most 8 (bf16) / 16 (split2) significant bits."""
+    if algo in GEMM_ALGOS:
+        return t
+    if algo not in GEMM_REDUCED:
+        raise ValueError(f"round_operand: unknown GEMM mode {algo!r}")
+    if t.dtype != torch.float32:
+        raise ValueError("round_operand: fp32 tensors only")
+    if algo == "bf16":
+        return t.bfloat16().float()
+    t = t.contiguous()
+    h = (t.view(torch.int32) & -65536).view(torch.float32)  # 0xffff0000: the high half
+    return h + (t - h).bfloat16().float()
+
+
 def gemm(a_kmajor: bool, b_kmajor: bool, As, Bs, M: int, N: int, K: int, algo: Optional[str] = None):
-    """Batched fp32 GEMM on the matrix cores (gnn_gemm_f32 / gnn_gemm_f32_split3):
-    C[b] = A[b]·B[b] with the layouts of include/gnn_layers.h; all problems share shapes and
-    row strides. Returns new (M x N) tensors."""
+    """Batched fp32 GEMM on the matrix cores (gnn_gemm_f32 / gnn_gemm_f32_split3, or
+    gnn_gemm_f32_split for the reduced modes): C[b] = A[b]·B[b] with the layouts of
+    include/gnn_layers.h; all problems share shapes and row strides. Returns new (M x N) tensors."""
     import ctypes
+    from functools import partial
 
     algo = algo or gemm_algo()
     dev = As[0].device
@@ -173,6 +206,12 @@ def gemm(a_kmajor: bool, b_kmajor: bool, As, Bs, M: int, N: int, K: int, algo: O
     L = _lib.lib()
     if algo == "split3":
         wsf, fn, name = L.gnn_gemm_f32_split3_workspace_bytes, L.gnn_gemm_f32_split3, "gnn_gemm_f32_split3"
+    elif algo in GEMM_REDUCED:
+        np_ = GEMM_PIECES[algo]
+        wsf, fn, name = (partial(L.gnn_gemm_f32_split_workspace_bytes, np_), partial(L.gnn_gemm_f32_split, np_),
+                         "gnn_gemm_f32_split")
+    elif algo != "f32":
+        raise ValueError(f"gemm: unknown algo {algo!r}")
     else:
         wsf, fn, name = L.gnn_gemm_f32_workspace_bytes, L.gnn_gemm_f32, "gnn_gemm_f32"
     wsb = wsf(M, N, K, nb)
@@ -194,7 +233,7 @@ def _mfma_fills(M: int, N: int, nb: int) -> bool:
     measured, it beats the vendor GEMM when it does (15.8k x 602 -> 512 pair: 175 vs 189 µs)
     and loses when a last round runs half empty (8.7k x 1024 -> 512 pair: 202 vs 171 µs)."""
     tiles = -(-M // 128) * -(-N // 128) * nb
-    if gemm_algo() == "split3":
+    if _split_kernel(gemm_algo()):  # split3 and its reduced modes route alike
         # at least one 128 x 128 tile per CU: the layer-2 products (512 rows: 32-64 tiles)
         # run 22-31 µs here against ~10 µs in the vendor's small-tile kernels
         return tiles >= 256
@@ -244,12 +283,12 @@ class LinearPairFn(torch.autograd.Function):
         if any(ctx.needs_input_grad[1 + n:]):
             # split over the sampled rows (gemm.hip pick_splits); split3 from 2048 rows (the
             # layer-2 weight gradient, 512 rows: 19 + 5 µs here vs ~7 µs in the vendor GEMM)
-            if ok and ((gemm_algo() == "split3" and M >= 2048) or (gemm_algo() == "f32" and K % 128)):
+            if ok and ((_split_kernel(gemm_algo()) and M >= 2048) or (gemm_algo() == "f32" and K % 128)):
                 # Measured (scripts/gemm_sweep.py, in the step): for 602 features the vendor
                 # kernels run at 66 TF/s (145 µs per product) against 95 µs here; for the
                 # 1024-wide layers hipBLASLt's tiles fit exactly and it is faster (79 vs 93 µs).
                 dWs = gemm(True, True, gs, xs, N, K, M)
-            elif gemm_algo() == "split3":
+            elif _split_kernel(gemm_algo()):
                 # small products on torch's default BLAS: switching the preferred library per
                 # call cost ~0.5 ms of host time per step (host-issue bound steps, measured)
                 dWs = [torch.mm(g.t(), x) for g, x in zip(gs, xs)]
@@ -352,6 +391,16 @@ def sage_norm(hB: Optional[torch.Tensor], hW: torch.Tensor, scale: torch.Tensor,
     return SageNormFn.apply(hB, hW, scale, offset, biasB, biasW, float(p), bool(training and p > 0), seed)
 
 
+def _head_bias_grad(dz: torch.Tensor) -> torch.Tensor:
+    """db = Σ_rows dz with the native step's fixed-order kernel (gnn_head_bias_grad_f32), so this path
+    and gnn_train_step_f32 give the same bits (torch's own reduction sums in another order)."""
+    M, C = dz.shape
+    db = torch.empty(C, dtype=torch.float32, device=dz.device)
+    _lib.check(_lib.lib().gnn_head_bias_grad_f32(dz.data_ptr(), M, C, db.data_ptr(), _stream(dz.device)),
+               "gnn_head_bias_grad_f32")
+    return db
+
+
 class HeadBCEFn(torch.autograd.Function):
     """GNN's head and loss (models.py:90-97 + utils.py:129-140, sigmoid_loss):
     BCEWithLogits(linear(dropout(normalize(x))), labels, weight 1/M, "sum") in one HIP pass
@@ -400,7 +449,7 @@ class HeadBCEFn(torch.autograd.Function):
                                                    dx.data_ptr(), D, _stream(dev)),
                    "gnn_head_bce_bwd_f32")
         dW = torch.mm(dz.t(), xd) if ctx.needs_input_grad[1] else None
-        db = dz.sum(0) if (has_bias and ctx.needs_input_grad[2]) else None
+        db = _head_bias_grad(dz) if (has_bias and ctx.needs_input_grad[2]) else None
         return dx, dW, db, None, None, None, None
 
 
@@ -473,7 +522,7 @@ class HeadCEFn(torch.autograd.Function):
                                                   dx.data_ptr(), D, lse.data_ptr(), _stream(dev)),
                    "gnn_head_ce_bwd_f32")
         dW = torch.mm(dz.t(), xd) if ctx.needs_input_grad[1] else None
-        db = dz.sum(0) if (has_bias and ctx.needs_input_grad[2]) else None
+        db = _head_bias_grad(dz) if (has_bias and ctx.needs_input_grad[2]) else None
         return dx, dW, db, None, None, None, None
 
 

@@ -30,7 +30,7 @@ from .models import loss as loss_fn
 
 class Trainer:
     def __init__(self, model: torch.nn.Module, lr: float, device, group=None, sigmoid_loss: bool = True,
-                 clip: float = 5.0):
+                 clip: float = 5.0, gemm=None):
         self.model = model
         self.device = torch.device(device)
         self.sigmoid_loss = sigmoid_loss
@@ -57,9 +57,16 @@ class Trainer:
 
             if ex.enabled():
                 try:
-                    self.executor = ex.NativeStep(model, sigmoid_loss=sigmoid_loss)
-                except ValueError:
+                    self.executor = ex.NativeStep(model, sigmoid_loss=sigmoid_loss, gemm=gemm)
+                except ValueError as e:
                     self.executor = None
+                    if gemm is not None:
+                        raise ValueError(f"Trainer: gemm={gemm!r} needs the native step executor ({e})") from e
+        # the layers' GEMM precision (NativeStep's ``gemm``: "split3", "split2", "bf16" or one name per
+        # layer) lives in the executor's descriptor; the Python path reads only GNN_GEMM_ALGO
+        if gemm is not None and self.executor is None:
+            raise ValueError("Trainer: gemm= needs the native step executor (a fused model on a GPU, "
+                             "GNN_NATIVE_STEP not 0); the Python path takes its GEMM mode from GNN_GEMM_ALGO")
         self.world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)

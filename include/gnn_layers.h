@@ -96,6 +96,35 @@ int gnn_gemm_f32_split3_indexed(int a_kmajor, int b_kmajor, int64_t M, int64_t N
                                 const float* const* B, int64_t ldb, const int64_t* const* ib, int64_t b_rows,
                                 float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The split kernel at a chosen piece count: the opt-in reduced-precision modes. fp32 operands and
+ * fp32 accumulation as above, fewer mantissa bits on the matrix-core operands. Every operand element
+ * x is replaced by a rounded x', and each output accumulates in fp32 the EXACT bf16 x bf16 products
+ * of the kept pieces, in split3's order:
+ *   pieces = 3 ("split3"): the entry points above, bit for bit.
+ *   pieces = 2 ("split2"): h = trunc_bf16(x) (split3's own h), r = x - h (exact), m = RNE_bf16(r);
+ *     x' = h + m, |x - x'| <= 2^-15 |x|. Per k step the four products m·m, m·h, h·m, h·h — split3's
+ *     list l·h, m·m, h·l, m·h, h·m, h·h without the two l products — i.e. the fp32-accumulated
+ *     product of the rounded operands (h + m)(h + m): no dropped cross term.
+ *   pieces = 1 ("bf16"): h = RNE_bf16(x) (round to nearest even, torch's x.bfloat16()); x' = h,
+ *     |x - x'| <= 2^-8 |x|. One product h·h per k step.
+ * For every output and k split, k runs ascending in steps of 16, one MFMA per piece product per
+ * step; the k-split count, the tail-tile plan, the tile map and the workspace are split3's for the
+ * same shape and batch count (at its 128 x 128 tile: GNN_GEMM_WIDE is ignored below 3 pieces). So
+ * on operands that already fit the kept pieces (<= 8 significant bits for bf16, <= 16 for split2)
+ * a reduced mode reproduces split3 bit for bit: the removed products are all ±0. Inputs below
+ * 2^-100 in magnitude, NaN and Inf are unspecified, as for split3. pieces outside 1..3: status -22
+ * before any device call (the workspace query returns 0). Operands of >= 2 GiB are refused below 3
+ * pieces. The indexed form is gnn_gemm_f32_split3_indexed's, bit-identical to the same mode's
+ * product of the gathered operands. */
+size_t gnn_gemm_f32_split_workspace_bytes(int pieces, int64_t M, int64_t N, int64_t K, int nbatch);
+int gnn_gemm_f32_split(int pieces, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
+                       const float* const* A, int64_t lda, const float* const* B, int64_t ldb, float* const* C,
+                       int64_t ldc, void* workspace, size_t workspace_bytes, void* stream);
+int gnn_gemm_f32_split_indexed(int pieces, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int nbatch,
+                               const float* const* A, int64_t lda, const int64_t* const* ia, int64_t a_rows,
+                               const float* const* B, int64_t ldb, const int64_t* const* ib, int64_t b_rows,
+                               float* const* C, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream);
+
 /* split3 over operands split ONCE into their three bf16 pieces ("p3"): gnn_gemm_p3_pack_f32 writes
  * an operand viewed as R rows (M for A, N for B) by K — element (r, k) = src[row(r)*ld + k]
  * (kmajor = 0) or src[row(k)*ld + r] (kmajor = 1), row() through idx when given — as three
@@ -150,6 +179,13 @@ int gnn_head_ce_bwd_f32(const float* X, int64_t ldx, int64_t M, int64_t D, const
                         const float* labels, int64_t ldl, const float* grad_loss, float p, uint64_t seed, int training,
                         const float* z, const float* norm, float* dz, float* dX, int64_t lddx, const float* lse,
                         void* stream);
+
+/* The head's bias gradient db[c] = Σ_rows dz[r][c] (dz M x C, row stride C) in a fixed order: one
+ * workgroup per class, each thread a strided set of rows, then a fixed tree — the kernel the native
+ * step (gnn_train_step_f32) runs for it, so the Python fused path (fused.HeadBCEFn / HeadCEFn) and
+ * the native step give the same bits, where a library reduction's order is its own. M = 0 writes
+ * zeros; C = 0 launches nothing. */
+int gnn_head_bias_grad_f32(const float* dz, int64_t M, int64_t C, float* db, void* stream);
 
 /* Evaluation head (head.hip): the forward above with training = 0 for a validation / test batch
  * (main.py:178-199, 217-241: model.eval(), forward, utils.loss, utils.calc_f1) — no dropout, no

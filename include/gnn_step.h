@@ -81,6 +81,17 @@
  *     GNN_SH_STAGE_LAYER's forward aggregation, or, if that layer is order 0, where the aggregation
  *     would have been issued — before the layer's GEMM. Timing records are written for aggregations
  *     only; the NSAMPLED == M check applies to aggregating SAGE layers only.
+ *     GNN_SL_GEMM: the precision of the layer's matrix-core products (gnn_layers.h,
+ *     gnn_gemm_f32_split). 0 = as the environment says (GNN_GEMM_ALGO: unset / split3, f32, or the
+ *     reduced modes split2 / bf16 process-wide), so every descriptor built before the slot had a
+ *     meaning keeps it (GNN_STEP_VERSION stays 1). 1, 2 or 3 = that many bf16 pieces per operand
+ *     (1: "bf16", 2: "split2", 3: split3) for every product of the layer that the step routes to the
+ *     split kernel: the forward pair, the input gradients, the weight gradients, their row-indexed
+ *     forms and their single-product launches under GNN_STEP_OVERLAP. The routing is split3's and
+ *     does not depend on the slot; products on the vendor GEMM stay fp32 sgemm, the head is not
+ *     touched, the workspace is unchanged, and gnn_eval_step_f32 honours the slot through the shared
+ *     forward. Any other value is refused like a bad loss kind (both *_workspace_bytes functions
+ *     return 0, nothing is launched, gnn_last_error() names the layer).
  */
 #ifndef GNN_STEP_H
 #define GNN_STEP_H
@@ -114,7 +125,7 @@ enum {
   GNN_SL_TROWPTR = 6, GNN_SL_TCOL = 7, GNN_SL_TVAL = 8, GNN_SL_SAMPLED = 9, GNN_SL_NSAMPLED = 10,
   GNN_SL_RMAP = 11, GNN_SL_WW = 12, GNN_SL_BW = 13, GNN_SL_WB = 14, GNN_SL_BB = 15, GNN_SL_SCALE = 16,
   GNN_SL_OFFSET = 17, GNN_SL_GWW = 18, GNN_SL_GBW = 19, GNN_SL_GWB = 20, GNN_SL_GBB = 21, GNN_SL_GSCALE = 22,
-  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24, GNN_SL_XKIND = 25, GNN_SL_DENSE = 26
+  GNN_SL_GOFFSET = 23, GNN_SL_SEED = 24, GNN_SL_XKIND = 25, GNN_SL_DENSE = 26, GNN_SL_GEMM = 27
 };
 
 size_t gnn_train_step_workspace_bytes(const int64_t* desc);

@@ -1,7 +1,9 @@
 """GPU microbench: the GraphSAGE-Reddit layer GEMM shapes (config 2) on gnn_gemm_f32 kernel
 variants (env knobs read per call: VARIANTS="GNN_GEMM_PF=2,GNN_GEMM_XCD=1;..." — ';' between
 variants, ',' between settings, '-' = defaults) and on the vendor GEMM (torch.matmul), with an fp64
-error check of every variant: |C - C64| <= 4e-6 (|A|·|B|) as in tests/test_gemm_gpu.py."""
+error check of every variant: |C - C64| <= 4e-6 (|A|·|B|) as in tests/test_gemm_gpu.py; under a
+reduced mode (GNN_GEMM_ALGO=split2 / bf16) A and B are the mode's rounded operands
+(fused.round_operand), and v<variant>_relerr_fp32 is the error against the unrounded product."""
 import json
 import os
 import sys
@@ -9,7 +11,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gnn_amd.fused import gemm  # noqa: E402
+from gnn_amd.fused import GEMM_REDUCED, gemm, gemm_algo, round_operand  # noqa: E402
 
 
 def timeit(fn, reps=20):
@@ -70,8 +72,14 @@ def main():
                 times[v].append(timeit(lambda: gemm(ak, bk, As, Bs, M, N, K)))
                 if rnd == 0:
                     Cs = gemm(ak, bk, As, Bs, M, N, K)
-                    err = max(float(((c.double() - c64).abs() / (s64 + 1e-30)).max())
-                              for c, c64, s64 in zip(Cs, C64, S64))
+                    rel = lambda R, S: max(float(((c.double() - r).abs() / (s + 1e-30)).max())  # noqa: E731
+                                           for c, r, s in zip(Cs, R, S))
+                    err = rel(C64, S64)
+                    if gemm_algo() in GEMM_REDUCED:
+                        row[f"v{v}_relerr_fp32"] = float(f"{err:.2e}")
+                        Ar = [round_operand(a, gemm_algo()).double() for a in As]
+                        Br = [round_operand(b, gemm_algo()).double() for b in Bs]
+                        err = rel([ref(a, b) for a, b in zip(Ar, Br)], [ref(a.abs(), b.abs()) for a, b in zip(Ar, Br)])
                     row[f"v{v}_relerr"] = float(f"{err:.2e}")
                     row[f"v{v}_ok"] = err <= 4e-6
         for v in variants:
