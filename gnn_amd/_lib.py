@@ -40,6 +40,9 @@ _SIGNATURES = {
                                     _VP]),
     "gnn_spmm_h16_config": (_INT, [_I64, _I64, _I64, _I64, _I64, _I64, _VP, _VP, _I64,
                                    ctypes.POINTER(ctypes.c_int32)]),
+    "gnn_spmm_graph_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "gnn_spmm_graph_f32": (_INT, [_VP, _VP, _VP, _I64, _I64, _I64, _I64, _I64, _VP, _I64, _INT, _VP, _I64, _I64, _VP,
+                                  _SZ, _VP]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

@@ -577,6 +577,33 @@ __global__ __launch_bounds__(256) void build_operand_t_kernel(
   }
 }
 
+// Row pointer and values of rows [row0, row0 + rows) of the resident graph as a block-local CSR
+// (gnn_spmm_graph_f32): rowptr[i] = indptr[row0 + i] - e0, val[e] = (float)(1.0 / degree(row)) —
+// build_operand_kernel's value with normfact = 1. One wave per row (wave `rows` writes the end).
+// The pointer is clamped to [0, nnz] and its two ends are pinned to 0 and nnz, so a device
+// indptr that disagrees with the host's e0 / nnz still gives the aggregation a row pointer whose
+// every entry indexes inside the block's nnz columns and values (wrong sums, no stray access).
+__global__ __launch_bounds__(256) void graph_block_kernel(
+    const int64_t* __restrict__ indptr, const int* __restrict__ degree, int64_t row0, int rows, int64_t e0,
+    int nnz, int* __restrict__ rowptr, float* __restrict__ val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i64 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i64 > rows) return;
+  const int i = (int)i64;
+  if (i == rows) {
+    if (lane == 0) rowptr[rows] = nnz;
+    return;
+  }
+  const int64_t lo = indptr[row0 + i] - e0;
+  const int64_t hi = indptr[row0 + i + 1] - e0;
+  const int b = i == 0 ? 0 : (int)min(max(lo, (int64_t)0), (int64_t)nnz);
+  const int e = i == rows - 1 ? nnz : (int)min(max(hi, (int64_t)0), (int64_t)nnz);
+  if (lane == 0) rowptr[i] = b;
+  if (b >= e) return;
+  const float w = (float)(1.0 / (double)degree[row0 + i]);
+  for (int64_t k = (int64_t)b + lane; k < e; k += 64) val[k] = w;
+}
+
 // COO index image of a CSR: indices[0][i] = row(i), indices[1][i] = col[i].
 __global__ __launch_bounds__(256) void csr_to_coo_indices_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, int nrows, int64_t nnz,
@@ -1779,6 +1806,69 @@ int gnn_spmm_csr_h16_f32(const int32_t* rowptr, const int32_t* col, const float*
     GNN_LAUNCHED("spmm_combine_kernel");
   }
   return 0;
+}
+
+// The aggregation's share is gnn_spmm_workspace_bytes(rows, nnz, F, 0) raised to a bound that
+// grows with rows and nnz, so one workspace sized for the largest block of a plan serves every
+// smaller one. default_unit's unit count itself is not monotone (the unit size doubles as rows get
+// longer); it never exceeds max(2048, min(nnz / 4, 1.25 rows) + nnz / 256) (units of >= 256 entries
+// for long rows, about two rows or >= 4 entries per unit for short ones).
+size_t gnn_spmm_graph_workspace_bytes(int64_t rows, int64_t nnz, int64_t F) {
+  const int64_t r = rows > 0 ? rows : 0, n = nnz > 0 ? nnz : 0;
+  const int64_t units = std::max<int64_t>(2048, std::min(ceil_div(n, 4), r + r / 4 + 2) + ceil_div(n, 256) + 1);
+  const size_t slab = align_up((size_t)(F > 0 ? F : 1), 4) * 2 * sizeof(float);
+  const size_t agg = std::max(align_up((size_t)units * slab, 256), gnn_spmm_workspace_bytes(r, n, F, 0));
+  return align_up(((size_t)r + 1) * sizeof(int32_t), 256) + align_up((size_t)n * sizeof(float), 256) + agg;
+}
+
+int gnn_spmm_graph_f32(const int64_t* indptr, const int32_t* indices, const int32_t* degree, int64_t num_nodes,
+                       int64_t row0, int64_t rows, int64_t e0, int64_t nnz, const void* X, int64_t ldx, int kind,
+                       float* Y, int64_t ldy, int64_t F, void* workspace, size_t workspace_bytes, void* stream) {
+  // the timing hook belongs to the aggregation launched below: a refused call clears it, as the
+  // aggregation entry points do
+  hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
+  g_ev_start = g_ev_stop = nullptr;
+  GNN_REQUIRE(kind == GNN_FEAT_F32 || kind == GNN_FEAT_F16 || kind == GNN_FEAT_BF16,
+              "gnn_spmm_graph_f32: kind %d is none of GNN_FEAT_F32 (0), GNN_FEAT_F16 (1), GNN_FEAT_BF16 (2)", kind);
+  GNN_REQUIRE(num_nodes >= 0 && row0 >= 0 && rows >= 0 && e0 >= 0 && nnz >= 0 && F >= 0,
+              "gnn_spmm_graph_f32: negative size (num_nodes, row0, rows, e0, nnz or F)");
+  GNN_REQUIRE(rows < INT_MAX && nnz < INT_MAX && num_nodes < INT_MAX,
+              "gnn_spmm_graph_f32: rows, nnz and num_nodes must be < 2^31");
+  GNN_REQUIRE(row0 <= num_nodes && rows <= num_nodes - row0, "gnn_spmm_graph_f32: row0 (%lld) + rows (%lld) > num_nodes (%lld)",
+              (long long)row0, (long long)rows, (long long)num_nodes);
+  GNN_REQUIRE(F <= ldx, "gnn_spmm_graph_f32: F (%lld) > ldx (%lld)", (long long)F, (long long)ldx);
+  GNN_REQUIRE(F <= ldy, "gnn_spmm_graph_f32: F (%lld) > ldy (%lld)", (long long)F, (long long)ldy);
+  if (kind != GNN_FEAT_F32) {  // what gnn_spmm_csr_h16_f32 refuses, before the block's launch
+    GNN_REQUIRE(F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0,
+                "gnn_spmm_graph_f32: 16-bit X: F (%lld), ldx (%lld) and ldy (%lld) must be multiples of 4",
+                (long long)F, (long long)ldx, (long long)ldy);
+    GNN_REQUIRE((uintptr_t)X % 8 == 0, "gnn_spmm_graph_f32: 16-bit X not 8-byte aligned");
+    GNN_REQUIRE((uintptr_t)Y % 16 == 0, "gnn_spmm_graph_f32: 16-bit X: Y not 16-byte aligned");
+  }
+  const size_t need = gnn_spmm_graph_workspace_bytes(rows, nnz, F);
+  GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_spmm_graph_f32: workspace too small (%zu < %zu)",
+              workspace ? workspace_bytes : (size_t)0, need);
+  GNN_REQUIRE((uintptr_t)workspace % 16 == 0, "gnn_spmm_graph_f32: workspace not 16-byte aligned");
+  if (rows == 0 || F == 0) return 0;
+  GNN_REQUIRE(indptr && degree && Y, "gnn_spmm_graph_f32: NULL indptr/degree/Y");
+  GNN_REQUIRE(nnz == 0 || (indices && X), "gnn_spmm_graph_f32: NULL indices/X");
+  char* ws = (char*)workspace;
+  int32_t* rowptr = (int32_t*)ws;
+  ws += align_up(((size_t)rows + 1) * sizeof(int32_t), 256);
+  float* val = (float*)ws;
+  ws += align_up((size_t)nnz * sizeof(float), 256);
+  const size_t rest = workspace_bytes - (size_t)(ws - (char*)workspace);
+  hipStream_t st = (hipStream_t)stream;
+  graph_block_kernel<<<dim3((unsigned)ceil_div(rows + 1, 4)), dim3(256), 0, st>>>(indptr, degree, row0, (int)rows, e0,
+                                                                                 (int)nnz, rowptr, val);
+  GNN_LAUNCHED("graph_block_kernel");
+  // the block's columns are the graph's own, read in place: the aggregation loads col per lane
+  const int32_t* col = indices ? indices + e0 : nullptr;
+  g_ev_start = ev0;
+  g_ev_stop = ev1;
+  if (kind == GNN_FEAT_F32)
+    return gnn_spmm_csr_f32(rowptr, col, val, rows, num_nodes, nnz, (const float*)X, ldx, Y, ldy, F, ws, rest, 0, st);
+  return gnn_spmm_csr_h16_f32(rowptr, col, val, rows, num_nodes, nnz, X, ldx, kind, Y, ldy, F, ws, rest, 0, st);
 }
 
 size_t gnn_segsort_workspace_bytes(int64_t nseg) { return segsort_ws(nseg); }

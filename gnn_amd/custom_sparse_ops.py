@@ -258,6 +258,20 @@ def csr_of(mat: "torch.Tensor | CsrOperand") -> CsrOperand:
     return plan
 
 
+def _kernel_width(dense: torch.Tensor, K: int, ldx: int) -> int:
+    """The width an aggregation runs over for ``dense`` (K rows of stride ldx): F rounded up to 4
+    when the rows are padded (stride a multiple of 4, base aligned for 4-wide vectors, every row's
+    storage holding the padded width), so the kernel takes its 4-wide vectors; else F."""
+    F = dense.shape[1]
+    esz = dense.element_size()
+    if F % 4 and ldx % 4 == 0 and dense.data_ptr() % (4 * esz) == 0:
+        F4 = F + (4 - F % 4)
+        avail = dense.untyped_storage().nbytes() // esz - dense.storage_offset()
+        if ldx >= F4 and (K - 1) * ldx + F4 <= avail:
+            return F4
+    return F
+
+
 def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: int = 0,
              residual: Optional[torch.Tensor] = None, rmap: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Y = A·X on the GPU (fp32). ``dense`` is fp32, row-major rows (stride(1) == 1); a padded
@@ -274,7 +288,6 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
     _require(dense.dtype in FEAT_KIND, "denseMat must be float32, float16 or bfloat16")
     _require(dense.stride(1) == 1 or dense.shape[1] <= 1, "denseMat must be contiguous")
     kind = FEAT_KIND[dense.dtype]
-    esz = dense.element_size()
     _require(kind == FEAT_F32 or (residual is None and rmap is None),
              "a float16 / bfloat16 denseMat takes no residual")
     M, K = op.shape
@@ -293,12 +306,7 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
                  "rmap must be a contiguous int32 CUDA tensor of M entries")
         _require(residual.dim() == 2 and residual.shape[1] == F and residual.stride(1) == 1,
                  "residual rows must be contiguous with F columns")
-    Fk = F
-    if F % 4 and ldx % 4 == 0 and dense.data_ptr() % (4 * esz) == 0 and rmap is None:
-        F4 = F + (4 - F % 4)
-        avail = dense.untyped_storage().nbytes() // esz - dense.storage_offset()
-        if ldx >= F4 and (K - 1) * ldx + F4 <= avail:
-            Fk = F4
+    Fk = _kernel_width(dense, K, ldx) if rmap is None else F
     if kind != FEAT_F32 and (Fk % 4 or ldx % 4 or dense.data_ptr() % 8):
         return spmm_csr(op, dense.float(), tag=tag, unit_nnz=unit_nnz)  # rows that do not fit: widen first
     # A padded input gets an output with the same row stride (line-aligned rows for the
@@ -334,6 +342,59 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
                                              dense.data_ptr(), ldx, out.data_ptr(), ldo, Fk,
                                              residual.data_ptr(), ldr, rmap.data_ptr(),
                                              ws.data_ptr(), wsb, unit_nnz, st), "gnn_spmm_csr_f32_ex")
+    return out if Fk == F else out[:, :F]
+
+
+def spmm_graph(graph, row0: int, rows: int, dense: torch.Tensor, e0: Optional[int] = None,
+               nnz: Optional[int] = None, tag: str = "fwd") -> torch.Tensor:
+    """Y = lap[row0 : row0 + rows, :] · X over the graph resident on the device (``graph`` a
+    sampler.DeviceGraph; weights 1/deg(row), create_coo_tensor's value with normfact = 1):
+    gnn_spmm_graph_f32. The block's columns are read in place from the graph's own index array
+    — no operand is built — and the sums are spmm_csr's on the same block, bit for bit, with the
+    same padded-width, 16-bit and output-stride rules. ``e0`` / ``nnz`` are indptr[row0] and the
+    block's entry count: taken from the NativeGraph's host row pointer (``graph.host_indptr``)
+    when omitted, never read back from the device."""
+    _require(dense.is_cuda, "denseMat must be a CUDA tensor")
+    _require(dense.dim() == 2, "denseMat must be 2-D")
+    _require(dense.dtype in FEAT_KIND, "denseMat must be float32, float16 or bfloat16")
+    _require(dense.stride(1) == 1 or dense.shape[1] <= 1, "denseMat must be contiguous")
+    N = int(graph.num_nodes)
+    row0, rows = int(row0), int(rows)
+    _require(0 <= row0 and 0 <= rows and row0 + rows <= N, f"rows [{row0}, {row0 + rows}) outside the graph's {N} rows")
+    _require(dense.shape[0] == N, f"size mismatch: graph of {N} nodes @ dense {tuple(dense.shape)}")
+    _require(dense.device == graph.device, "graph and denseMat must be on the same device")
+    if e0 is None or nnz is None:
+        hp = getattr(graph, "host_indptr", None)
+        _require(hp is not None, "spmm_graph: pass e0 and nnz (this graph keeps no host row pointer)")
+        e0 = int(hp[row0])
+        nnz = int(hp[row0 + rows]) - e0
+    e0, nnz = int(e0), int(nnz)
+    kind = FEAT_KIND[dense.dtype]
+    F = dense.shape[1]
+    ldx = dense.stride(0) if N > 1 else max(F, 1)
+    dev = dense.device
+    Fk = _kernel_width(dense, N, ldx)
+    if kind != FEAT_F32 and (Fk % 4 or ldx % 4 or dense.data_ptr() % 8):
+        return spmm_graph(graph, row0, rows, dense.float(), e0, nnz, tag=tag)  # rows that do not fit: widen first
+    ldo = ldx if (Fk != F and ldx <= 2 * Fk) else Fk
+    with _lib.on_device(dev):
+        out = torch.empty((rows, ldo), dtype=torch.float32, device=dev)
+        if rows == 0 or F == 0:
+            return out[:, :F]
+        L = _lib.lib()
+        wsb = L.gnn_spmm_graph_workspace_bytes(rows, nnz, Fk)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        if _timing_enabled:
+            e_0 = torch.cuda.Event(enable_timing=True)
+            e_1 = torch.cuda.Event(enable_timing=True)
+            e_0.record()  # creates the underlying hipEvent; the library re-records it
+            e_1.record()
+            L.gnn_spmm_set_timing_events(e_0.cuda_event, e_1.cuda_event)
+            record_timing(tag, e_0, e_1, rows, N, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False,
+                          x_kind=kind)
+        _lib.check(L.gnn_spmm_graph_f32(_ptr(graph.indptr), _ptr(graph.indices), _ptr(graph.degree), N, row0, rows,
+                                        e0, nnz, dense.data_ptr(), ldx, kind, out.data_ptr(), ldo, Fk,
+                                        ws.data_ptr(), wsb, _stream(dev)), "gnn_spmm_graph_f32")
     return out if Fk == F else out[:, :F]
 
 

@@ -246,6 +246,9 @@ class DeviceGraph:
             dev = torch.device("cuda", torch.cuda.current_device())  # where a bare 'cuda' allocates
         self.device = dev
         self.num_nodes = graph.num_nodes
+        # the host's row pointer (numpy int64, shared with the NativeGraph): block offsets and entry
+        # counts of custom_sparse_ops.spmm_graph come from here, never from the device
+        self.host_indptr = graph.indptr
         self.indptr = torch.from_numpy(graph.indptr).to(dev)
         self.indices = torch.from_numpy(graph.indices).to(dev)
         # row degrees as int32 (one 4-byte load per kept entry for the transposed values)

@@ -232,6 +232,23 @@ class Trainer:
             self.model.train(was_training)
         return ev.result()
 
+    def evaluate_exact(self, graph, feats, nodes, labels, mode: Optional[int] = None) -> dict:
+        """Scores ``nodes`` against ``labels`` with the full neighbourhood of every node — no
+        sampler, no importance weights: the model run layer by layer over the whole graph
+        (gnn_amd.inference.ExactInference, made once per graph and cached), in eval semantics;
+        the model's training mode is restored. Returns the keys of ``Evaluator.result()``."""
+        from .inference import ExactInference
+
+        cached = getattr(self, "_exact", None)
+        if cached is None or cached[0] is not graph:
+            cached = self._exact = (graph, ExactInference(self.model, graph, self.device))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return cached[1].evaluate(feats, nodes, labels, sigmoid_loss=self.sigmoid_loss, mode=mode)
+        finally:
+            self.model.train(was_training)
+
 
 class Evaluator:
     """Accumulates the loss and the per-class prediction counts of evaluation batches on the
@@ -254,6 +271,7 @@ class Evaluator:
         self.rows = []  # per batch, known on the host
         self._buf = None  # int32 [capacity, 3 C + 1]: a batch's counts, then its loss's bits
         self.native_batches = 0
+        self.counts = None  # set by result()
 
     def _native(self, x0, adjs, sampled_nodes, labels) -> bool:
         return (self.executor is not None
@@ -288,6 +306,13 @@ class Evaluator:
                     self.model.train()
             loss = loss.detach().to(torch.float32)
             counts = metrics.prediction_counts(out, labels, self.mode)
+        self.add_counts(loss, counts, int(labels.shape[0]))
+        return loss, counts
+
+    def add_counts(self, loss, counts, rows: int) -> None:
+        """One batch already scored elsewhere (inference.ExactInference.evaluate: a chunk of nodes
+        through the evaluation head): its mean loss (fp32 device scalar) and int32 counts [3, C]
+        over ``rows`` rows go into the buffer as ``add`` puts its own; synchronises nothing."""
         n, width = len(self.rows), counts.numel() + 1
         if self._buf is None or n == self._buf.shape[0]:
             grown = torch.empty((max(16, 2 * n), width), dtype=torch.int32, device=counts.device)
@@ -296,8 +321,7 @@ class Evaluator:
             self._buf = grown
         self._buf[n, :width - 1] = counts.reshape(-1)
         self._buf[n, width - 1:] = loss.reshape(1).view(torch.int32)
-        self.rows.append(int(labels.shape[0]))
-        return loss, counts
+        self.rows.append(int(rows))
 
     def predict(self, x0, adjs, sampled_nodes) -> torch.Tensor:
         """The logits [M, C] of one batch (model.eval(), no dropout), on the device."""
@@ -328,6 +352,7 @@ class Evaluator:
         rows = [float(r) for r in self.rows]
         total = sum(rows)
         pooled = counts.sum(axis=0)
+        self.counts = pooled  # int64 [3, C] on the host: (tp, fp, fn) of the whole pass
         micro, macro = metrics.f1_from_counts(pooled[0], pooled[1], pooled[2], self.mode)
         per_batch = [metrics.f1_from_counts(c[0], c[1], c[2], self.mode)[0] for c in counts]
         return {"micro_f1": micro, "macro_f1": macro,

@@ -112,6 +112,43 @@ int gnn_spmm_csr_h16_f32(const int32_t* rowptr, const int32_t* col, const float*
 int gnn_spmm_h16_config(int64_t M, int64_t K, int64_t nnz, int64_t F, int64_t ldx, int64_t ldy,
                         const void* X, const void* Y, int64_t unit_nnz, int32_t out[8]);
 
+/* Aggregation over rows [row0, row0 + rows) of the graph resident on the device (the canonical CSR
+ * a LADIES extraction reads, gnn_extract.h: int64 indptr[num_nodes + 1], int32 indices, int32 row
+ * degrees), for full-neighbourhood inference:
+ *     Y[i, 0:F] = sum over e in [indptr[row0+i], indptr[row0+i+1]) of w_i * X[indices[e], 0:F],
+ *     w_i = (float)(1.0 / (double)degree[row0+i])
+ * — gnn_build_operand_f32's value with normfact = 1. This is lap[rows, :] · X, the expectation of
+ * the operand the reference's sampler draws (sampler.py:113-139: adj = U[:, after_nodes] scaled by
+ * 1/(s·p), whose mean over the draw is U = lap[rows, :]); every sampled layer of this project
+ * estimates it. X has num_nodes rows (kind GNN_FEAT_F32, or GNN_FEAT_F16 / GNN_FEAT_BF16 rows read as
+ * gnn_spmm_csr_h16_f32 reads them; ldx in elements of X); rows of Y are block-local; empty rows
+ * store zeros.
+ *
+ * e0 = indptr[row0] and nnz = indptr[row0 + rows] - e0 are the host's copies (offsets into the
+ * graph are int64: the graph may hold 2^31 entries or more, a block may not). One small kernel
+ * writes the block's int32 row pointer (indptr[row0+i] - e0, clamped to [0, nnz] with its ends
+ * pinned to 0 and nnz, so a device indptr that disagrees with e0 / nnz cannot make the
+ * aggregation read outside the block) and its nnz weights into the workspace; the sums are then
+ * gnn_spmm_csr_f32 / gnn_spmm_csr_h16_f32 on (that pointer, indices + e0, the weights): the
+ * columns are read in place, and kernel choice, launch geometry and result are those of that call
+ * on the materialised block, bit for bit.
+ *
+ * Same contract as above (stream-ordered, no allocation, no host synchronisation,
+ * graph-capturable, the timing hook goes to the aggregation's main kernel). Refused with
+ * GNN_EINVAL before anything is launched: a negative size, rows, nnz or num_nodes >= 2^31,
+ * row0 + rows > num_nodes, F > ldx or F > ldy, a kind other than 0, 1, 2, a workspace smaller than
+ * gnn_spmm_graph_workspace_bytes(rows, nnz, F) or not 16-byte aligned, and for 16-bit X whatever
+ * gnn_spmm_csr_h16_f32 refuses. That size is the row pointer, the weights and the aggregation's
+ * gnn_spmm_workspace_bytes(rows, nnz, F, 0), each rounded up to 256 bytes — the last raised to a
+ * bound that grows with rows and with nnz (the unit count of gnn_spmm_default_unit_nnz does not),
+ * so the size is monotone in both and a workspace sized for a plan's largest block serves all. */
+size_t gnn_spmm_graph_workspace_bytes(int64_t rows, int64_t nnz, int64_t F);
+int gnn_spmm_graph_f32(const int64_t* indptr, const int32_t* indices, const int32_t* degree,
+                       int64_t num_nodes, int64_t row0, int64_t rows, int64_t e0, int64_t nnz,
+                       const void* X, int64_t ldx, int kind,
+                       float* Y, int64_t ldy, int64_t F,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Optional timing hook: when set, the NEXT gnn_spmm_csr_f32 / gnn_spmm_csr_h16_f32 call on this thread launches its
  * main aggregation kernel with `start` / `stop` as the dispatch's own start and end timestamps
  * (hipExtLaunchKernel: hipEventElapsedTime(start, stop) = the kernel's duration, as rocprofv3
