@@ -43,6 +43,14 @@ _SIGNATURES = {
     "gnn_spmm_graph_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "gnn_spmm_graph_f32": (_INT, [_VP, _VP, _VP, _I64, _I64, _I64, _I64, _I64, _VP, _I64, _INT, _VP, _I64, _I64, _VP,
                                   _SZ, _VP]),
+    "gnn_spmm_rows_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "gnn_spmm_rows_f32": (_INT, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _INT, _VP, _I64, _I64,
+                                 _VP, _SZ, _VP, _VP]),
+    "gnn_closure_table_bytes": (_SZ, [_I64]),
+    "gnn_closure_workspace_bytes": (_SZ, [_I64]),
+    "gnn_closure_mark": (_INT, [_VP, _VP, _I64, _VP, _I64, ctypes.c_int32, _VP, _VP, _VP, _SZ, _VP]),
+    "gnn_closure_list": (_INT, [_VP, _I64, _VP, _I64, _VP]),
+    "gnn_closure_rank": (_INT, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

@@ -604,6 +604,58 @@ __global__ __launch_bounds__(256) void graph_block_kernel(
   for (int64_t k = (int64_t)b + lane; k < e; k += 64) val[k] = w;
 }
 
+// Block-local CSR of the graph rows rows[0..M) with the columns relabelled to positions in a node
+// set (gnn_spmm_rows_f32): rowptr from the host's degree scan rowseg, clamped and pinned as above;
+// col[e] = the position of the entry's column in the set of the membership table tab (closure.hip /
+// extract.hip's word: x = the bits of 32 node ids, y = the members below them; one 8-byte load per
+// entry), val[e] = (float)(1.0 / degree(row)). One wave per row, its entries over the lanes (wave M
+// writes the end). Every entry position below nnz is written by exactly one row (consecutive rows
+// share their clamped bound), and an entry that cannot be resolved — a column outside the set or
+// not below K, a row id outside the graph, a scan that gives the row more entries than the graph
+// holds — is stored as column 0 with value 0 and raises err bit 0: the aggregation reads X rows
+// below K whatever the inputs hold.
+__global__ __launch_bounds__(256) void rows_block_kernel(
+    const int64_t* __restrict__ indptr, const int* __restrict__ indices, const int* __restrict__ degree,
+    int num_nodes, const int* __restrict__ rows, int M, const int* __restrict__ rowseg, int nnz,
+    const uint2* __restrict__ tab, int K, int* __restrict__ rowptr, int* __restrict__ col, float* __restrict__ val,
+    int* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i64 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i64 > M) return;
+  const int i = (int)i64;
+  if (i == M) {
+    if (lane == 0) rowptr[M] = nnz;
+    return;
+  }
+  const int b = i == 0 ? 0 : min(max(rowseg[i], 0), nnz);
+  const int e = i == M - 1 ? nnz : min(max(rowseg[i + 1], 0), nnz);
+  if (lane == 0) rowptr[i] = b;
+  if (b >= e) return;
+  const int r = rows[i];
+  const bool inside = (unsigned)r < (unsigned)num_nodes;
+  const int64_t src = inside ? indptr[r] : 0;
+  const int64_t len = inside ? indptr[r + 1] - src : 0;
+  const float w = inside ? (float)(1.0 / (double)degree[r]) : 0.0f;
+  bool bad = false;
+  for (int64_t k = (int64_t)b + lane; k < e; k += 64) {
+    const int64_t j = k - b;
+    int p = -1;
+    if (j < len) {
+      const int c = indices[src + j];
+      if ((unsigned)c < (unsigned)num_nodes) {
+        const uint2 wd = tab[c >> 5];
+        const unsigned sh = (unsigned)c & 31u;
+        if ((wd.x >> sh) & 1u) p = (int)wd.y + __builtin_popcount(wd.x & ((1u << sh) - 1u));
+      }
+    }
+    const bool ok = p >= 0 && p < K;
+    col[k] = ok ? p : 0;
+    val[k] = ok ? w : 0.0f;
+    bad |= !ok;
+  }
+  if (err && bad) atomicOr(err, 1);
+}
+
 // COO index image of a CSR: indices[0][i] = row(i), indices[1][i] = col[i].
 __global__ __launch_bounds__(256) void csr_to_coo_indices_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, int nrows, int64_t nnz,
@@ -1869,6 +1921,69 @@ int gnn_spmm_graph_f32(const int64_t* indptr, const int32_t* indices, const int3
   if (kind == GNN_FEAT_F32)
     return gnn_spmm_csr_f32(rowptr, col, val, rows, num_nodes, nnz, (const float*)X, ldx, Y, ldy, F, ws, rest, 0, st);
   return gnn_spmm_csr_h16_f32(rowptr, col, val, rows, num_nodes, nnz, X, ldx, kind, Y, ldy, F, ws, rest, 0, st);
+}
+
+// The row pointer, the relabelled columns, the weights and the aggregation's share. The last is
+// gnn_spmm_graph_workspace_bytes's monotone bound on the unit count, cut at nnz / 4 + 1 (a unit
+// never holds fewer than 4 entries: default_unit), itself monotone — so the few-row blocks of a
+// small closure do not pay the 2,048-unit floor of that bound.
+size_t gnn_spmm_rows_workspace_bytes(int64_t rows, int64_t nnz, int64_t F) {
+  const int64_t r = rows > 0 ? rows : 0, n = nnz > 0 ? nnz : 0;
+  const int64_t bound = std::max<int64_t>(2048, std::min(ceil_div(n, 4), r + r / 4 + 2) + ceil_div(n, 256) + 1);
+  const int64_t units = std::min(bound, ceil_div(n, 4) + 1);
+  const size_t slab = align_up((size_t)(F > 0 ? F : 1), 4) * 2 * sizeof(float);
+  const size_t agg = std::max(align_up((size_t)units * slab, 256), gnn_spmm_workspace_bytes(r, n, F, 0));
+  return align_up(((size_t)r + 1) * sizeof(int32_t), 256) + 2 * align_up((size_t)n * sizeof(float), 256) + agg;
+}
+
+int gnn_spmm_rows_f32(const int64_t* indptr, const int32_t* indices, const int32_t* degree, int64_t num_nodes,
+                      const int32_t* rows, int64_t M, const int32_t* rowseg, int64_t nnz, const void* table, int64_t K,
+                      const void* X, int64_t ldx, int kind, float* Y, int64_t ldy, int64_t F, void* workspace,
+                      size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;  // as gnn_spmm_graph_f32: a refused call clears the hook
+  g_ev_start = g_ev_stop = nullptr;
+  GNN_REQUIRE(kind == GNN_FEAT_F32 || kind == GNN_FEAT_F16 || kind == GNN_FEAT_BF16,
+              "gnn_spmm_rows_f32: kind %d is none of GNN_FEAT_F32 (0), GNN_FEAT_F16 (1), GNN_FEAT_BF16 (2)", kind);
+  GNN_REQUIRE(num_nodes >= 0 && M >= 0 && nnz >= 0 && K >= 0 && F >= 0,
+              "gnn_spmm_rows_f32: negative size (num_nodes, M, nnz, K or F)");
+  GNN_REQUIRE(M < INT_MAX && nnz < INT_MAX && num_nodes < INT_MAX && K < INT_MAX,
+              "gnn_spmm_rows_f32: M, nnz, num_nodes and K must be < 2^31");
+  GNN_REQUIRE(K <= num_nodes, "gnn_spmm_rows_f32: K (%lld) > num_nodes (%lld)", (long long)K, (long long)num_nodes);
+  GNN_REQUIRE(F <= ldx, "gnn_spmm_rows_f32: F (%lld) > ldx (%lld)", (long long)F, (long long)ldx);
+  GNN_REQUIRE(F <= ldy, "gnn_spmm_rows_f32: F (%lld) > ldy (%lld)", (long long)F, (long long)ldy);
+  if (kind != GNN_FEAT_F32) {
+    GNN_REQUIRE(F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0,
+                "gnn_spmm_rows_f32: 16-bit X: F (%lld), ldx (%lld) and ldy (%lld) must be multiples of 4",
+                (long long)F, (long long)ldx, (long long)ldy);
+    GNN_REQUIRE((uintptr_t)X % 8 == 0, "gnn_spmm_rows_f32: 16-bit X not 8-byte aligned");
+    GNN_REQUIRE((uintptr_t)Y % 16 == 0, "gnn_spmm_rows_f32: 16-bit X: Y not 16-byte aligned");
+  }
+  const size_t need = gnn_spmm_rows_workspace_bytes(M, nnz, F);
+  GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_spmm_rows_f32: workspace too small (%zu < %zu)",
+              workspace ? workspace_bytes : (size_t)0, need);
+  GNN_REQUIRE((uintptr_t)workspace % 16 == 0, "gnn_spmm_rows_f32: workspace not 16-byte aligned");
+  if (M == 0 || F == 0) return 0;
+  GNN_REQUIRE(indptr && degree && rows && rowseg && Y, "gnn_spmm_rows_f32: NULL indptr/degree/rows/rowseg/Y");
+  GNN_REQUIRE(table != nullptr && (uintptr_t)table % 8 == 0, "gnn_spmm_rows_f32: NULL or misaligned table");
+  GNN_REQUIRE(nnz == 0 || (indices && X), "gnn_spmm_rows_f32: NULL indices/X");
+  char* ws = (char*)workspace;
+  int32_t* rowptr = (int32_t*)ws;
+  ws += align_up(((size_t)M + 1) * sizeof(int32_t), 256);
+  int32_t* col = (int32_t*)ws;
+  ws += align_up((size_t)nnz * sizeof(int32_t), 256);
+  float* val = (float*)ws;
+  ws += align_up((size_t)nnz * sizeof(float), 256);
+  const size_t rest = workspace_bytes - (size_t)(ws - (char*)workspace);
+  hipStream_t st = (hipStream_t)stream;
+  rows_block_kernel<<<dim3((unsigned)ceil_div(M + 1, 4)), dim3(256), 0, st>>>(
+      indptr, indices, degree, (int)num_nodes, rows, (int)M, rowseg, (int)nnz, (const uint2*)table, (int)K, rowptr, col,
+      val, err_flag);
+  GNN_LAUNCHED("rows_block_kernel");
+  g_ev_start = ev0;
+  g_ev_stop = ev1;
+  if (kind == GNN_FEAT_F32)
+    return gnn_spmm_csr_f32(rowptr, col, val, M, K, nnz, (const float*)X, ldx, Y, ldy, F, ws, rest, 0, st);
+  return gnn_spmm_csr_h16_f32(rowptr, col, val, M, K, nnz, X, ldx, kind, Y, ldy, F, ws, rest, 0, st);
 }
 
 size_t gnn_segsort_workspace_bytes(int64_t nseg) { return segsort_ws(nseg); }

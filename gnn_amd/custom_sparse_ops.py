@@ -398,6 +398,101 @@ def spmm_graph(graph, row0: int, rows: int, dense: torch.Tensor, e0: Optional[in
     return out if Fk == F else out[:, :F]
 
 
+def spmm_rows(graph, rows: torch.Tensor, rowseg: torch.Tensor, nnz: int, table: torch.Tensor, K: int,
+              dense: torch.Tensor, tag: str = "fwd", err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y = lap[rows, :][:, S] · X over the graph resident on the device, S the node set of
+    ``table`` (closure_mark's membership table, K members) and ``dense`` its K rows in ascending
+    node order: gnn_spmm_rows_f32. ``rows`` is an int32 list of node ids, ``rowseg`` (int32, M + 1)
+    the host-made exclusive scan of their degrees, ``nnz`` its total. Weights 1/deg(row); the sums
+    are spmm_csr's on the materialised operand, bit for bit, with spmm_graph's padded-width, 16-bit
+    and output-stride rules. A column outside S contributes nothing and raises bit 0 of ``err`` (an
+    int32 CUDA word; default ``graph.err``)."""
+    _require(dense.is_cuda, "denseMat must be a CUDA tensor")
+    _require(dense.dim() == 2, "denseMat must be 2-D")
+    _require(dense.dtype in FEAT_KIND, "denseMat must be float32, float16 or bfloat16")
+    _require(dense.stride(1) == 1 or dense.shape[1] <= 1, "denseMat must be contiguous")
+    for name, t in (("rows", rows), ("rowseg", rowseg)):
+        _require(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), f"{name} must be contiguous int32 CUDA")
+    N, M, K, nnz = int(graph.num_nodes), int(rows.numel()), int(K), int(nnz)
+    _require(rowseg.numel() == M + 1, "rowseg must have M + 1 entries")
+    _require(dense.shape[0] == K, f"size mismatch: a set of {K} nodes @ dense {tuple(dense.shape)}")
+    _require(dense.device == graph.device and table.device == graph.device,
+             "graph, table and denseMat must be on the same device")
+    L = _lib.lib()
+    _require(table.is_contiguous() and table.numel() * table.element_size() >= L.gnn_closure_table_bytes(N),
+             "table must hold gnn_closure_table_bytes(num_nodes) bytes")
+    kind = FEAT_KIND[dense.dtype]
+    F = dense.shape[1]
+    ldx = dense.stride(0) if K > 1 else max(F, 1)
+    dev = dense.device
+    Fk = _kernel_width(dense, K, ldx)
+    if kind != FEAT_F32 and (Fk % 4 or ldx % 4 or dense.data_ptr() % 8):
+        return spmm_rows(graph, rows, rowseg, nnz, table, K, dense.float(), tag=tag, err=err)  # rows that do not fit: widen first
+    ldo = ldx if (Fk != F and ldx <= 2 * Fk) else Fk
+    with _lib.on_device(dev):
+        out = torch.empty((M, ldo), dtype=torch.float32, device=dev)
+        if M == 0 or F == 0:
+            return out[:, :F]
+        wsb = L.gnn_spmm_rows_workspace_bytes(M, nnz, Fk)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        if _timing_enabled:
+            e_0 = torch.cuda.Event(enable_timing=True)
+            e_1 = torch.cuda.Event(enable_timing=True)
+            e_0.record()  # creates the underlying hipEvent; the library re-records it
+            e_1.record()
+            L.gnn_spmm_set_timing_events(e_0.cuda_event, e_1.cuda_event)
+            record_timing(tag, e_0, e_1, M, K, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False,
+                          x_kind=kind)
+        _lib.check(L.gnn_spmm_rows_f32(_ptr(graph.indptr), _ptr(graph.indices), _ptr(graph.degree), N, _ptr(rows), M,
+                                       _ptr(rowseg), nnz, table.data_ptr(), K, dense.data_ptr(), ldx, kind,
+                                       out.data_ptr(), ldo, Fk, ws.data_ptr(), wsb, _ptr(graph.err if err is None else err),
+                                       _stream(dev)), "gnn_spmm_rows_f32")
+    return out if Fk == F else out[:, :F]
+
+
+def closure_mark(graph, seeds: torch.Tensor, expand: bool) -> "tuple[torch.Tensor, torch.Tensor]":
+    """(table, count) of the node set ``seeds`` (int32 CUDA, any order, repeats allowed) — with
+    ``expand`` joined by every column of lap[seeds, :] — over the resident ``graph``
+    (gnn_closure_mark): the membership table (uint8 storage of gnn_closure_table_bytes) and the
+    set's size as a device int64 scalar. Stream-ordered; reading the count is the caller's sync."""
+    _require(seeds.is_cuda and seeds.dtype == torch.int32 and seeds.is_contiguous(),
+             "seeds must be contiguous int32 CUDA")
+    _require(seeds.device == graph.device, "graph and seeds must be on the same device")
+    dev, N = seeds.device, int(graph.num_nodes)
+    L = _lib.lib()
+    with _lib.on_device(dev):
+        table = torch.empty(L.gnn_closure_table_bytes(N), dtype=torch.uint8, device=dev)
+        count = torch.empty((), dtype=torch.int64, device=dev)
+        wsb = L.gnn_closure_workspace_bytes(N)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(L.gnn_closure_mark(_ptr(graph.indptr), _ptr(graph.indices), N, _ptr(seeds), int(seeds.numel()),
+                                      int(bool(expand)), table.data_ptr(), count.data_ptr(), ws.data_ptr(), wsb,
+                                      _stream(dev)), "gnn_closure_mark")
+    return table, count
+
+
+def closure_list(table: torch.Tensor, num_nodes: int, count: int) -> torch.Tensor:
+    """The ``count`` members of the table's set in ascending order, int32 (gnn_closure_list)."""
+    dev = table.device
+    with _lib.on_device(dev):
+        out = torch.empty(int(count), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().gnn_closure_list(table.data_ptr(), int(num_nodes), _ptr(out), int(count), _stream(dev)),
+                   "gnn_closure_list")
+    return out
+
+
+def closure_rank(table: torch.Tensor, num_nodes: int, ids: torch.Tensor, err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 positions of ``ids`` (int32 CUDA) in the table's ascending set (gnn_closure_rank); an
+    id outside the set gets 0 and raises bit 0 of ``err`` (int32 CUDA, optional)."""
+    _require(ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous(), "ids must be contiguous int32 CUDA")
+    dev = table.device
+    with _lib.on_device(dev):
+        pos = torch.empty(int(ids.numel()), dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().gnn_closure_rank(table.data_ptr(), int(num_nodes), _ptr(ids), int(ids.numel()),
+                                               _ptr(pos), _ptr(err), _stream(dev)), "gnn_closure_rank")
+    return pos
+
+
 def _on_cpu(mat1, mat2) -> bool:
     """Both operands on the CPU: the config-1 torch.sparse.mm branch."""
     return (isinstance(mat1, torch.Tensor) and isinstance(mat2, torch.Tensor) and mat1.device.type == "cpu"

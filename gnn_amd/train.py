@@ -232,11 +232,13 @@ class Trainer:
             self.model.train(was_training)
         return ev.result()
 
-    def evaluate_exact(self, graph, feats, nodes, labels, mode: Optional[int] = None) -> dict:
+    def evaluate_exact(self, graph, feats, nodes, labels, mode: Optional[int] = None, scope="graph") -> dict:
         """Scores ``nodes`` against ``labels`` with the full neighbourhood of every node — no
         sampler, no importance weights: the model run layer by layer over the whole graph
         (gnn_amd.inference.ExactInference, made once per graph and cached), in eval semantics;
-        the model's training mode is restored. Returns the keys of ``Evaluator.result()``."""
+        the model's training mode is restored. Returns the keys of ``Evaluator.result()``.
+        ``scope="closure"`` runs the layers over the k-hop closure of ``nodes`` only (the same
+        scores at the closure's cost; ``ExactInference.logits``)."""
         from .inference import ExactInference
 
         cached = getattr(self, "_exact", None)
@@ -245,7 +247,8 @@ class Trainer:
         was_training = self.model.training
         self.model.eval()
         try:
-            return cached[1].evaluate(feats, nodes, labels, sigmoid_loss=self.sigmoid_loss, mode=mode)
+            return cached[1].evaluate(feats, nodes, labels, sigmoid_loss=self.sigmoid_loss, mode=mode,
+                                      scope=scope)
         finally:
             self.model.train(was_training)
 

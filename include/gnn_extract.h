@@ -95,6 +95,37 @@ int gnn_colcount_add(void* ctx, const int64_t* rows, int64_t n, int64_t* nlive, 
 int gnn_colcount_reset(void* ctx);
 void gnn_colcount_destroy(void* ctx);
 
+/* Node sets on the device, for inference restricted to a query set's k-hop closure (closure.hip).
+ * A set S over num_nodes nodes is its membership table, the word of the extraction above: one
+ * 8-byte word (uint32 x, uint32 y) per 32 node ids — x = the ids of [32 w, 32 w + 32) as bits,
+ * y = the number of members below 32 w — and one trailing word (x = 0, y = |S|). The position of
+ * node c in ascending S is y + popcount(x & ((1 << c % 32) - 1)) of word c / 32.
+ * gnn_closure_table_bytes(num_nodes): the table's size; gnn_closure_workspace_bytes(num_nodes):
+ * gnn_closure_mark's scratch (the scan's chunk sums). Both are rounded up to 256 bytes.
+ *
+ * mark: table = the membership table of seeds int32[n] (any order, repeats allowed) and, with
+ *   expand != 0, of every column of lap[seeds, :] as well (indices[indptr[s] .. indptr[s+1]) for
+ *   each seed s; the graph as gnn_ladies_extract_f32 takes it). *count (device int64) = |S|.
+ *   A wave per seed, its row's entries over the lanes; bits are OR-ed atomically (relaxed), the
+ *   ranks are a chunked scan: five launches in stream order, no workgroup waits for another.
+ *   Seeds and columns outside [0, num_nodes) are skipped. n = 0 gives the empty table, count 0.
+ * list: out[0 .. min(|S|, cap)) = the members in ascending order; nothing is written at or past cap.
+ * rank: pos[i] (int64, the index type of gnn_gather_rows_f32) = the position of ids[i] in S; an id
+ *   outside S gets position 0 and ORs 1 into err_flag (device int32, optional).
+ *
+ * Conventions as above: device pointers, stream-ordered, no allocation, no host synchronisation.
+ * Refused with GNN_EINVAL before anything is launched: a negative size, num_nodes or n >= 2^31, a
+ * NULL or misaligned table, a NULL count / seeds / ids / pos / out where one is read or written, a
+ * workspace that is NULL, too small or not 16-byte aligned. */
+size_t gnn_closure_table_bytes(int64_t num_nodes);
+size_t gnn_closure_workspace_bytes(int64_t num_nodes);
+int gnn_closure_mark(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, const int32_t* seeds, int64_t n,
+                     int32_t expand, void* table, int64_t* count, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int gnn_closure_list(const void* table, int64_t num_nodes, int32_t* out, int64_t cap, void* stream);
+int gnn_closure_rank(const void* table, int64_t num_nodes, const int32_t* ids, int64_t n, int64_t* pos,
+                     int32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,40 @@ int gnn_spmm_graph_f32(const int64_t* indptr, const int32_t* indices, const int3
                        float* Y, int64_t ldy, int64_t F,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same aggregation over a list of graph rows, with the columns relabelled to positions in a
+ * node set — one layer of inference restricted to a query set's closure (gnn_extract.h:
+ * gnn_closure_*):
+ *     Y[i, 0:F] = w_i * sum over the entries e of graph row rows[i] of X[pos(indices[e]), 0:F],
+ *     w_i = (float)(1.0 / (double)degree[rows[i]])
+ * rows int32[M]: node ids in any order (repeats allowed); table: the membership table of the set
+ * (gnn_closure_mark's, over num_nodes nodes), whose K members index X's K rows: pos(c) is c's
+ * position in the ascending set. rowseg int32[M+1] (device) is the host-made exclusive scan of the
+ * rows' degrees and nnz = rowseg[M] its total, as gnn_ladies_extract_f32 takes its offsets.
+ *
+ * One kernel writes the block-local CSR into the workspace: the row pointer from rowseg (clamped
+ * to [0, nnz], ends pinned), col[e] = pos(indices[..]) (one 8-byte table load per entry, a row's
+ * entries over a wave's lanes) and val[e] = w_i. The set is ascending and pos monotone, so columns
+ * stay ascending per row. The sums are then gnn_spmm_csr_f32 / gnn_spmm_csr_h16_f32 on that
+ * operand: kernel choice, geometry and result are that call's on the materialised block, bit for
+ * bit. An entry whose column is not in the set (or any entry the inputs do not resolve: a position
+ * not below K, a row id outside the graph, a scan longer than the graph's row) is stored as
+ * column 0 with value 0 and ORs 1 into err_flag (device int32, optional): every stored column is
+ * below K, so the aggregation stays inside X whatever the inputs hold.
+ *
+ * Contract and refusals as gnn_spmm_graph_f32 (M in place of rows), plus K >= 2^31, K > num_nodes
+ * and a NULL table. The workspace, gnn_spmm_rows_workspace_bytes(M, nnz, F), is the row pointer,
+ * the columns, the weights and gnn_spmm_graph_workspace_bytes's monotone bound for the
+ * aggregation (its unit count cut at nnz / 4 + 1: a unit never holds fewer than 4 entries, so a
+ * few-row block does not pay that bound's 2,048-unit floor), each rounded up to 256 bytes; monotone
+ * in rows and nnz, never below gnn_spmm_workspace_bytes(M, nnz, F, 0). */
+size_t gnn_spmm_rows_workspace_bytes(int64_t rows, int64_t nnz, int64_t F);
+int gnn_spmm_rows_f32(const int64_t* indptr, const int32_t* indices, const int32_t* degree,
+                      int64_t num_nodes, const int32_t* rows, int64_t M, const int32_t* rowseg,
+                      int64_t nnz, const void* table, int64_t K,
+                      const void* X, int64_t ldx, int kind,
+                      float* Y, int64_t ldy, int64_t F,
+                      void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream);
+
 /* Optional timing hook: when set, the NEXT gnn_spmm_csr_f32 / gnn_spmm_csr_h16_f32 call on this thread launches its
  * main aggregation kernel with `start` / `stop` as the dispatch's own start and end timestamps
  * (hipExtLaunchKernel: hipEventElapsedTime(start, stop) = the kernel's duration, as rocprofv3
