@@ -675,6 +675,20 @@ int64_t bwd_grid(int64_t M, int64_t D, bool agg = false) {
   return std::max<int64_t>(1, ceil_div(M, 4) < cap ? ceil_div(M, 4) : cap);
 }
 
+// What the backward launches for (M, D): the form, its float4 count per lane (NV of the one-wave
+// kernel, NVH of the split one) and its grid, which is also the number of partial rows the
+// finalize sums. One place for the launch and for gnn_sage_norm_config.
+struct BwdPlan {
+  bool split;
+  int nv;
+  int64_t grid;
+};
+
+BwdPlan bwd_plan(int64_t M, int64_t D, bool agg) {
+  const bool split = use_bwd2(D);
+  return BwdPlan{split, (int)ceil_div(split ? D / 2 : D, 256), bwd_grid(M, D, agg)};
+}
+
 template <bool AGG>
 BwdFn bwd_fn(int nv) {
   switch (nv) {
@@ -736,21 +750,33 @@ size_t gnn_sage_norm_bwd_workspace_bytes(int64_t M, int64_t D) {
   return gnn::align_up((size_t)G * NRED * (size_t)(D > 0 ? D : 1) * sizeof(float), 256);
 }
 
+int gnn_sage_norm_config(int64_t M, int64_t D, int agg, int* split_rows, int* nv, int* grid) {
+  GNN_REQUIRE(M >= 0 && M < INT_MAX, "gnn_sage_norm_config: M out of range");
+  GNN_REQUIRE(D > 0 && D <= SN_MAXV * 256 && D % 4 == 0, "gnn_sage_norm_config: D = %lld must be a multiple of 4 in "
+              "(0, 2048]", (long long)D);
+  const BwdPlan plan = bwd_plan(M, D, agg != 0);
+  if (split_rows) *split_rows = plan.split ? 1 : 0;
+  if (nv) *nv = plan.nv;
+  if (grid) *grid = (int)plan.grid;
+  return 0;
+}
+
 }  // extern "C"
 
 namespace {
 
-int sage_norm_bwd(const GradSrc& src, bool agg, const float* hB, int64_t ldb, int64_t D1, const float* hW,
-                  int64_t ldw, int64_t D2, const float* biasB, const float* biasW, const float* scale,
+// fn: the entry that was called (errors are reported under its name)
+int sage_norm_bwd(const char* fn, const GradSrc& src, bool agg, const float* hB, int64_t ldb, int64_t D1,
+                  const float* hW, int64_t ldw, int64_t D2, const float* biasB, const float* biasW, const float* scale,
                   const float* mean, const float* rstd, int64_t M, float p_drop, uint64_t seed, int training,
                   float* dhB, float* dhW, float* dscale, float* doffset, float* dbiasB, float* dbiasW,
                   void* workspace, size_t workspace_bytes, void* stream) {
   const float* gY = agg ? src.G : src.gY;
   const int64_t ldg = agg ? 4 : src.ldg;
-  int rc = check_shapes("gnn_sage_norm_bwd_f32", D1, D2, M, hB, ldb, hW, ldw, biasB, biasW);
+  int rc = check_shapes(fn, D1, D2, M, hB, ldb, hW, ldw, biasB, biasW);
   if (rc) return rc;
-  GNN_REQUIRE(scale && dscale && doffset, "gnn_sage_norm_bwd_f32: NULL pointer");
-  GNN_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, "gnn_sage_norm_bwd_f32: p_drop must be in [0, 1)");
+  GNN_REQUIRE(scale && dscale && doffset, "%s: NULL pointer", fn);
+  GNN_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, "%s: p_drop must be in [0, 1)", fn);
   const int D = (int)(D1 + D2);
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) {
@@ -760,22 +786,23 @@ int sage_norm_bwd(const GradSrc& src, bool agg, const float* hB, int64_t ldb, in
     if (dbiasW && D2) GNN_HIP(hipMemsetAsync(dbiasW, 0, (size_t)D2 * 4, st), "dbiasW memset");
     return 0;
   }
-  GNN_REQUIRE(gY && mean && rstd && (D1 == 0 || dhB) && (D2 == 0 || dhW), "gnn_sage_norm_bwd_f32: NULL pointer");
-  GNN_REQUIRE(ldg % 4 == 0 && (uintptr_t)gY % 16 == 0, "gnn_sage_norm_bwd_f32: gY must be 16-byte aligned rows");
-  GNN_REQUIRE(D1 == 0 || (uintptr_t)dhB % 16 == 0, "gnn_sage_norm_bwd_f32: dhB not 16-byte aligned");
-  GNN_REQUIRE(D2 == 0 || (uintptr_t)dhW % 16 == 0, "gnn_sage_norm_bwd_f32: dhW not 16-byte aligned");
+  GNN_REQUIRE(gY && mean && rstd && (D1 == 0 || dhB) && (D2 == 0 || dhW), "%s: NULL pointer", fn);
+  GNN_REQUIRE(ldg % 4 == 0 && (uintptr_t)gY % 16 == 0, "%s: gY must be 16-byte aligned rows", fn);
+  GNN_REQUIRE(D1 == 0 || (uintptr_t)dhB % 16 == 0, "%s: dhB not 16-byte aligned", fn);
+  GNN_REQUIRE(D2 == 0 || (uintptr_t)dhW % 16 == 0, "%s: dhW not 16-byte aligned", fn);
   GNN_REQUIRE(workspace && workspace_bytes >= gnn_sage_norm_bwd_workspace_bytes(M, D),
-              "gnn_sage_norm_bwd_f32: workspace too small");
-  const int64_t G = bwd_grid(M, D, agg);
+              "%s: workspace too small", fn);
+  const BwdPlan plan = bwd_plan(M, D, agg);
+  const int64_t G = plan.grid;
   const float inv_keep = 1.0f / (1.0f - p_drop);
   float* partial = (float*)workspace;
-  if (use_bwd2(D)) {
-    hipLaunchKernelGGL(agg ? bwd2_fn<true>((int)ceil_div(D / 2, 256)) : bwd2_fn<false>((int)ceil_div(D / 2, 256)),
+  if (plan.split) {
+    hipLaunchKernelGGL(agg ? bwd2_fn<true>(plan.nv) : bwd2_fn<false>(plan.nv),
                        dim3((unsigned)G), dim3(256), (size_t)2 * D * sizeof(float), st, src, hB ? hB : hW, ldb, biasB,
                        (int)D1, hW, ldw, biasW, D, scale, mean, rstd, (int)M, p_drop, inv_keep, seed, training,
                        dhB ? dhB : dhW, dhW, partial);
   } else {
-    hipLaunchKernelGGL(agg ? bwd_fn<true>((int)ceil_div(D, 256)) : bwd_fn<false>((int)ceil_div(D, 256)),
+    hipLaunchKernelGGL(agg ? bwd_fn<true>(plan.nv) : bwd_fn<false>(plan.nv),
                        dim3((unsigned)G), dim3(256), (size_t)4 * D * sizeof(float), st, src, hB ? hB : hW, ldb, biasB,
                        (int)D1, hW, ldw, biasW, D, scale, mean, rstd, (int)M, p_drop, inv_keep, seed, training,
                        dhB ? dhB : dhW, dhW, partial);
@@ -799,7 +826,8 @@ int gnn_sage_norm_bwd_f32(const float* gY, int64_t ldg, const float* hB, int64_t
   GradSrc src{};
   src.gY = gY;
   src.ldg = ldg;
-  return sage_norm_bwd(src, false, hB, ldb, D1, hW, ldw, D2, biasB, biasW, scale, mean, rstd, M, p_drop, seed,
+  return sage_norm_bwd("gnn_sage_norm_bwd_f32", src, false, hB, ldb, D1, hW, ldw, D2, biasB, biasW, scale, mean,
+                       rstd, M, p_drop, seed,
                        training, dhB, dhW, dscale, doffset, dbiasB, dbiasW, workspace, workspace_bytes, stream);
 }
 
@@ -825,7 +853,8 @@ int gnn_sage_norm_bwd_agg_f32(const int32_t* t_rowptr, const int32_t* t_col, con
   src.R = R;
   src.ldr = ldr;
   src.rmap = rmap;
-  return sage_norm_bwd(src, true, hB, ldb, D1, hW, ldw, D2, biasB, biasW, scale, mean, rstd, M, p_drop, seed,
+  return sage_norm_bwd("gnn_sage_norm_bwd_agg_f32", src, true, hB, ldb, D1, hW, ldw, D2, biasB, biasW, scale, mean,
+                       rstd, M, p_drop, seed,
                        training, dhB, dhW, dscale, doffset, dbiasB, dbiasW, workspace, workspace_bytes, stream);
 }
 

@@ -58,6 +58,18 @@ int gnn_sage_norm_bwd_agg_f32(const int32_t* t_rowptr, const int32_t* t_col, con
                               float* doffset, float* dbiasB, float* dbiasW, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* What the backward (agg = 0: gnn_sage_norm_bwd_f32, 1: gnn_sage_norm_bwd_agg_f32) launches for M
+ * rows of width D, for tests and tools that must know which kernel a shape reaches:
+ *   split_rows  1: two waves per row (sage_norm_bwd2_kernel<nv>), 0: one (sage_norm_bwd_kernel<nv>)
+ *   nv          float4 per lane of that kernel (of half a row in the split form)
+ *   grid        its workgroups = the partial rows the finalize kernel sums (1 at M = 0, where
+ *               nothing is launched)
+ * A pure host function of its arguments and of GNN_SAGE_BWD1, GNN_SAGE_BWD_GRID (read once per
+ * process) and GNN_SAGE_BWD2_GRID(_AGG): no HIP call. The forward runs
+ * sage_norm_fwd_kernel<ceil(D / 256)> on ceil(M / 4) workgroups for every shape. Output
+ * pointers may be NULL. Non-zero when D is not a multiple of 4 in (0, 2048]. */
+int gnn_sage_norm_config(int64_t M, int64_t D, int agg, int* split_rows, int* nv, int* grid);
+
 /* ---------------------------------------------------------------------------------
  * fp32 GEMMs of the layers on gfx950 MFMA (gemm.hip): C[b] = A[b] · B[b] for b < nbatch
  * (1..4 problems of one shape in one launch; A, B, C are HOST arrays of device pointers).

@@ -119,6 +119,53 @@ def test_workspace_and_config():
     assert L.gnn_segsort_workspace_bytes(100) >= 800
 
 
+def _sage_config(M, D, agg=0):
+    s, nv, grid = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    assert _lib.lib().gnn_sage_norm_config(M, D, agg, ctypes.byref(s), ctypes.byref(nv), ctypes.byref(grid)) == 0
+    return s.value, nv.value, grid.value
+
+
+def test_sage_norm_config(monkeypatch):
+    """The layer tail's backward dispatch (sage.hip): which form, how many float4 per lane and which grid a
+    shape gets, by default and under each environment override; the workspace query covers every grid."""
+    L = _lib.lib()
+    for k in ("GNN_SAGE_BWD1", "GNN_SAGE_BWD_GRID", "GNN_SAGE_BWD2_GRID", "GNN_SAGE_BWD2_GRID_AGG"):
+        monkeypatch.delenv(k, raising=False)
+    one_wave = {4: 1, 100: 1, 256: 1, 260: 2, 508: 2, 516: 3, 1020: 4, 1028: 5, 1284: 6, 1540: 7, 2044: 8}
+    split = {512: 1, 520: 2, 1024: 2, 1032: 3, 1536: 3, 1544: 4, 2048: 4}
+    for agg in (0, 1):
+        for D, nv in one_wave.items():  # D % 8 != 0 or D < 512: one wave per row, NV = ceil(D / 256)
+            assert _sage_config(9, D, agg) == (0, nv, 3), D
+            assert _sage_config(3100, D, agg) == (0, nv, 768), D  # capped at 768 workgroups of 4 rows
+            assert _sage_config(3072, D, agg) == (0, nv, 768) and _sage_config(3068, D, agg) == (0, nv, 767)
+        for D, nvh in split.items():  # two waves per row, NVH = ceil(D / 2 / 256)
+            assert _sage_config(9, D, agg) == (1, nvh, 5), D
+            assert _sage_config(4100, D, agg) == (1, nvh, 1024), D  # capped at 1,024 workgroups of 2 rows
+            assert _sage_config(2046, D, agg) == (1, nvh, 1023), D
+        assert _sage_config(0, 1024, agg) == (1, 2, 1) and _sage_config(0, 100, agg) == (0, 1, 1)
+    # the split grid's overrides are read per call, one for each entry
+    monkeypatch.setenv("GNN_SAGE_BWD2_GRID", "3")
+    assert _sage_config(13, 1032, 0) == (1, 3, 3) and _sage_config(13, 1032, 1) == (1, 3, 7)
+    assert _sage_config(13, 1028, 0) == (0, 5, 4)  # not the one-wave form's
+    monkeypatch.setenv("GNN_SAGE_BWD2_GRID_AGG", "2048")
+    assert _sage_config(4100, 1024, 1) == (1, 2, 2048) and _sage_config(4100, 1024, 0) == (1, 2, 3)
+    monkeypatch.setenv("GNN_SAGE_BWD2_GRID", "2049")  # out of range: the default
+    assert _sage_config(4100, 1024, 0) == (1, 2, 1024)
+    for M, D in ((4100, 1024), (9, 512), (100000, 2048), (3100, 2044), (3100, 100)):
+        assert L.gnn_sage_norm_bwd_workspace_bytes(M, D) >= max(_sage_config(M, D, a)[2] for a in (0, 1)) * 3 * D * 4
+    # GNN_SAGE_BWD1 forces the one-wave form on the split widths
+    monkeypatch.setenv("GNN_SAGE_BWD1", "1")
+    for D, nv in ((512, 2), (1024, 4), (2048, 8)):
+        assert _sage_config(9, D) == (0, nv, 3) and _sage_config(4100, D, 1) == (0, nv, 768)
+        assert L.gnn_sage_norm_bwd_workspace_bytes(4100, D) >= 768 * 3 * D * 4
+    # refused widths; output pointers are optional
+    for D in (2052, 6, 0, -4):
+        assert L.gnn_sage_norm_config(9, D, 0, None, None, None) != 0
+        assert b"gnn_sage_norm_config" in L.gnn_last_error()
+    assert L.gnn_sage_norm_config(-1, 100, 0, None, None, None) != 0
+    assert L.gnn_sage_norm_config(9, 100, 0, None, None, None) == 0
+
+
 _GEMM_WS_SHAPES = [(512, 602, 15809, 2), (512, 1024, 8689, 2), (15809, 512, 602, 2), (8689, 512, 1024, 2),
                    (8689, 1024, 512, 2), (101, 131, 3001, 1), (1, 5, 3, 1)]
 # per shape: (gnn_gemm_f32_, gnn_gemm_f32_split3_, gnn_gemm_p3_)workspace_bytes, recorded from the library

@@ -2,9 +2,11 @@
 and whole GraphSAGE/GCN training steps on the GPU against the reference's golden step.
 
 Floating-point tolerance: the epilogue reduces 512-2048 values per row (mean, variance)
-and 15k rows per column (d(scale), d(offset)) in a different order than torch: compared
-with rtol = 1e-4, atol = 1e-5 against an fp64 evaluation of the same expression, the
-same bound torch's own fp32 kernels meet (checked alongside).
+and 15k rows per column (d(scale), d(offset)) in a different order than torch: outputs and
+input gradients are compared with rtol = 1e-4, atol = 1e-5 against an fp64 evaluation of the
+same expression (torch's own fp32 evaluation of it on the CPU differs from fp64 by at most
+1.1e-6 absolute in the input gradients), the column sums with atol = 1e-4. Every kernel
+instantiation, stride and grid of the tail is covered in tests/test_sage_tail_gpu.py.
 """
 import numpy as np
 import pytest
@@ -50,10 +52,11 @@ def test_sage_norm_matches_torch(dev, D1, D2, M, bias):
     y = sage_norm(*leaves[:4], p=0.1, training=False, biasB=leaves[4], biasW=leaves[5])
     y.backward(gY.to(dev))
     np.testing.assert_allclose(y.detach().cpu().numpy(), y64.detach().numpy(), rtol=1e-4, atol=1e-5)
-    for a, b in zip(leaves, leaves64):
+    # hB, hW: elementwise; scale, offset and the biases: column sums over M rows in another order
+    for i, (a, b) in enumerate(zip(leaves, leaves64)):
         if a is None:
             continue
-        np.testing.assert_allclose(a.grad.cpu().numpy(), b.grad.numpy(), rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(a.grad.cpu().numpy(), b.grad.numpy(), rtol=1e-4, atol=1e-5 if i < 2 else 1e-4)
 
 
 def test_sage_norm_dropout_masks(dev):
