@@ -51,6 +51,11 @@ _SIGNATURES = {
     "gnn_closure_mark": (_INT, [_VP, _VP, _I64, _VP, _I64, ctypes.c_int32, _VP, _VP, _VP, _SZ, _VP]),
     "gnn_closure_list": (_INT, [_VP, _I64, _VP, _I64, _VP]),
     "gnn_closure_rank": (_INT, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
+    "gnn_nbr_workspace_bytes": (_SZ, [_I64]),
+    "gnn_nbr_rowptr": (_INT, [_VP, _I64, _I64, _VP, _I64, ctypes.c_int32, _VP, _VP, _VP, _SZ, _VP, _VP]),
+    "gnn_nbr_draw": (_INT, [_VP, _VP, _I64, _I64, _VP, _I64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, _VP, _VP,
+                            _VP, _I64, _VP, _VP]),
+    "gnn_nbr_relabel": (_INT, [_VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

@@ -126,6 +126,55 @@ int gnn_closure_list(const void* table, int64_t num_nodes, int32_t* out, int64_t
 int gnn_closure_rank(const void* table, int64_t num_nodes, const int32_t* ids, int64_t n, int64_t* pos,
                      int32_t* err_flag, void* stream);
 
+/* Node-wise neighbour sampling over the resident graph (neighbor.hip): the layer operand of a
+ * GraphSAGE-style draw with a fanout per layer. The graph as above (lap's canonical CSR, no stored
+ * values: every entry of row r weighs 1/deg(r)); num_entries = the length of indices. Output row i
+ * (node rows[i]; any order, repeats allowed) keeps k_i = min(deg(rows[i]), fanout) entries of its
+ * graph row, a uniform k_i-subset without replacement, each with the weight
+ * (float)(1.0 / (double)k_i) — an unbiased estimate of lap[rows[i], :], and the row itself when
+ * deg <= fanout. 1 <= fanout <= 64.
+ *
+ * The draw is a pure integer function of (seed, layer, node id, deg, fanout), so a row's entries
+ * do not depend on its place in the batch or on the device. With mix32 the "lowbias32" hash of
+ * the dropout masks (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16),
+ * in 32-bit arithmetic:
+ *   key = mix32((mix32(lo32(seed) ^ 0x9e3779b9) ^ hi32(seed)) + layer * 0x85EBCA6B)
+ *   rk  = mix32(node ^ key)
+ *   deg <= fanout: every entry. Otherwise (Floyd), for s = 0 .. k-1: j = deg - k + s,
+ *   u = mix32(rk ^ mix32(s + 0x632BE5AB)), t = (uint64(u) * (j + 1)) >> 32; insert j if t is in
+ *   the set already, else t. The kept entries are those positions of the row, ascending.
+ *
+ * rowptr: rowptr int32[M+1] = the exclusive scan of k_i, *total (device int64) = rowptr[M];
+ *   workspace = gnn_nbr_workspace_bytes(M) bytes (the scan's chunk sums), 16-byte aligned.
+ * draw: ids int32[cap] / val fp32[cap] receive, at rowptr[i] .. rowptr[i+1], row i's kept global
+ *   column ids in ascending order and their weights; rowptr as gnn_nbr_rowptr made it with the same
+ *   rows and fanout; cap = the capacity of ids / val (M * fanout always suffices). Only the kept
+ *   entries of a row are read.
+ * relabel: col[e] = the position of ids[e] in the ascending set of a gnn_closure_mark table, as
+ *   int32 (a CsrOperand's column type), e < n. An id outside the set becomes column 0, with
+ *   val[e] = 0 when val is given.
+ * A layer's input set is gnn_closure_mark(seeds = rows ++ ids, expand = 0) + gnn_closure_list.
+ *
+ * Memory safety does not depend on the contents of the device arrays: a row id outside
+ * [0, num_nodes), or a row pointer outside [0, num_entries] or running backwards, gives the row
+ * k = 0; a row whose output range leaves [0, cap] is skipped; a column id outside the graph is
+ * stored as id -1 with weight 0 (gnn_closure_mark skips it, relabel makes it column 0). Each
+ * case ORs 1 into err_flag (device int32, optional).
+ *
+ * Conventions as above: device pointers, stream-ordered, no allocation, no host synchronisation.
+ * Refused with GNN_EINVAL before anything is launched: a negative size, num_nodes, M or n >= 2^31,
+ * M * fanout >= 2^31, fanout outside [1, 64], a NULL pointer where one is read or written, a
+ * misaligned table, a workspace that is NULL, too small or not 16-byte aligned. */
+size_t gnn_nbr_workspace_bytes(int64_t M);
+int gnn_nbr_rowptr(const int64_t* indptr, int64_t num_nodes, int64_t num_entries, const int32_t* rows, int64_t M,
+                   int32_t fanout, int32_t* rowptr, int64_t* total, void* workspace, size_t workspace_bytes,
+                   int32_t* err_flag, void* stream);
+int gnn_nbr_draw(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
+                 const int32_t* rows, int64_t M, int32_t fanout, uint64_t seed, int32_t layer, const int32_t* rowptr,
+                 int32_t* ids, float* val, int64_t cap, int32_t* err_flag, void* stream);
+int gnn_nbr_relabel(const void* table, int64_t num_nodes, const int32_t* ids, int64_t n, int32_t* col, float* val,
+                    int32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
