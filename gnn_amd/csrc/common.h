@@ -16,7 +16,16 @@ int fail(int code, const char* fmt, ...);
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// out[0..n] = exclusive prefix of in[0..n) (out[n] = total), one workgroup (spmm.hip).
+// Floats per load that every row of X and Y allows (4: 16-byte, 2: 8-byte, else 1): the SpMM's and
+// the fp32 gathers' vector width.
+inline int pick_vw(int64_t F, int64_t ldx, int64_t ldy, const void* X, const void* Y) {
+  const uintptr_t px = (uintptr_t)X, py = (uintptr_t)Y;
+  if (F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && px % 16 == 0 && py % 16 == 0) return 4;
+  if (F % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && px % 8 == 0 && py % 8 == 0) return 2;
+  return 1;
+}
+
+// out[0..n] = exclusive prefix of in[0..n) (out[n] = total), one workgroup (operand.hip).
 int launch_scan_exclusive(const int* in, int n, int* out, hipStream_t st);
 
 // Whether gnn_spmm_csr_f32(_ex) runs this call shape as spmm_row_kernel with one wave per row

@@ -104,6 +104,19 @@ def record_timing(tag, e0, e1, M, K, nnz, F, Fk, ldx, ldy, xptr, yptr, unit_nnz,
                                  x_bytes=2 if x_kind else 4)))
 
 
+def _arm_timing(L, tag, *shape, x_kind: int = 0) -> None:
+    """With timing on: arm two events for the aggregation the caller launches next and append its
+    record (``shape``: record_timing's arguments from M on)."""
+    if not _timing_enabled:
+        return
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()  # creates the underlying hipEvent; the library re-records it
+    e1.record()
+    L.gnn_spmm_set_timing_events(e0.cuda_event, e1.cuda_event)
+    record_timing(tag, e0, e1, *shape, x_kind=x_kind)
+
+
 def _h16_kernel_name(fp32_name: str, kind: int) -> str:
     """The 16-bit twin of an fp32 main kernel at VW 4 (same G / NJ / U / WPR): as rocprofv3 lists it."""
     stem, args = fp32_name.rstrip(">").split("<")
@@ -320,14 +333,8 @@ def spmm_csr(op: CsrOperand, dense: torch.Tensor, tag: str = "fwd", unit_nnz: in
         wsb = L.gnn_spmm_workspace_bytes(M, op.nnz, Fk, unit_nnz)
         ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
         st = _stream(dev)
-        if _timing_enabled:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()  # creates the underlying hipEvent; the library re-records it
-            e1.record()
-            L.gnn_spmm_set_timing_events(e0.cuda_event, e1.cuda_event)
-            record_timing(tag, e0, e1, M, K, op.nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), unit_nnz,
-                          residual.shape[0] if rmap is not None else 0, rmap is not None, x_kind=kind)
+        _arm_timing(L, tag, M, K, op.nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), unit_nnz,
+                    residual.shape[0] if rmap is not None else 0, rmap is not None, x_kind=kind)
         if kind != FEAT_F32:
             _lib.check(L.gnn_spmm_csr_h16_f32(_ptr(op.rowptr), _ptr(op.col), _ptr(op.val), M, K, op.nnz,
                                               dense.data_ptr(), ldx, kind, out.data_ptr(), ldo, Fk,
@@ -384,14 +391,7 @@ def spmm_graph(graph, row0: int, rows: int, dense: torch.Tensor, e0: Optional[in
         L = _lib.lib()
         wsb = L.gnn_spmm_graph_workspace_bytes(rows, nnz, Fk)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        if _timing_enabled:
-            e_0 = torch.cuda.Event(enable_timing=True)
-            e_1 = torch.cuda.Event(enable_timing=True)
-            e_0.record()  # creates the underlying hipEvent; the library re-records it
-            e_1.record()
-            L.gnn_spmm_set_timing_events(e_0.cuda_event, e_1.cuda_event)
-            record_timing(tag, e_0, e_1, rows, N, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False,
-                          x_kind=kind)
+        _arm_timing(L, tag, rows, N, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False, x_kind=kind)
         _lib.check(L.gnn_spmm_graph_f32(_ptr(graph.indptr), _ptr(graph.indices), _ptr(graph.degree), N, row0, rows,
                                         e0, nnz, dense.data_ptr(), ldx, kind, out.data_ptr(), ldo, Fk,
                                         ws.data_ptr(), wsb, _stream(dev)), "gnn_spmm_graph_f32")
@@ -435,14 +435,7 @@ def spmm_rows(graph, rows: torch.Tensor, rowseg: torch.Tensor, nnz: int, table: 
             return out[:, :F]
         wsb = L.gnn_spmm_rows_workspace_bytes(M, nnz, Fk)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        if _timing_enabled:
-            e_0 = torch.cuda.Event(enable_timing=True)
-            e_1 = torch.cuda.Event(enable_timing=True)
-            e_0.record()  # creates the underlying hipEvent; the library re-records it
-            e_1.record()
-            L.gnn_spmm_set_timing_events(e_0.cuda_event, e_1.cuda_event)
-            record_timing(tag, e_0, e_1, M, K, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False,
-                          x_kind=kind)
+        _arm_timing(L, tag, M, K, nnz, F, Fk, ldx, ldo, dense.data_ptr(), out.data_ptr(), 0, 0, False, x_kind=kind)
         _lib.check(L.gnn_spmm_rows_f32(_ptr(graph.indptr), _ptr(graph.indices), _ptr(graph.degree), N, _ptr(rows), M,
                                        _ptr(rowseg), nnz, table.data_ptr(), K, dense.data_ptr(), ldx, kind,
                                        out.data_ptr(), ldo, Fk, ws.data_ptr(), wsb, _ptr(graph.err if err is None else err),

@@ -75,6 +75,230 @@ def test_argument_validation_without_gpu():
     assert L.gnn_spmm_csr_f32(None, None, None, 0, 4, 0, None, 8, None, 8, 8, None, 0, 0, None) == 0
 
 
+# ---- refusals of the aggregation entry points ----------------------------------------------------
+# Every call below is refused (or returns early) on the host, before the first HIP call, so the
+# pointers are never read: _P stands for "some 16-byte aligned address", _BIG for "a workspace large
+# enough". The default shape is a 4-row operand over K = 64 with 57 entries and unit_nnz = 16 (the
+# unit kernel, 4 units, so the workspace is needed).
+_P = 0x10000
+_BIG = 1 << 40
+_CSR = dict(rowptr=_P, col=_P, val=_P, M=4, K=64, nnz=57, X=_P, ldx=12, Y=_P, ldy=12, F=12, ws=_P, wsb=_BIG, unit=16)
+_BLOCK = dict(indptr=_P, indices=_P, degree=_P, N=64, nnz=57, X=_P, ldx=12, kind=0, Y=_P, ldy=12, F=12, ws=_P,
+              wsb=_BIG)
+
+
+def _call_csr_f32(L, **kw):
+    a = dict(_CSR, **kw)
+    return L.gnn_spmm_csr_f32(a["rowptr"], a["col"], a["val"], a["M"], a["K"], a["nnz"], a["X"], a["ldx"], a["Y"],
+                              a["ldy"], a["F"], a["ws"], a["wsb"], a["unit"], None)
+
+
+def _call_csr_f32_ex(L, **kw):
+    a = dict(_CSR, R=None, ldr=0, rmap=None)
+    a.update(kw)
+    return L.gnn_spmm_csr_f32_ex(a["rowptr"], a["col"], a["val"], a["M"], a["K"], a["nnz"], a["X"], a["ldx"], a["Y"],
+                                 a["ldy"], a["F"], a["R"], a["ldr"], a["rmap"], a["ws"], a["wsb"], a["unit"], None)
+
+
+def _call_csr_h16_f32(L, **kw):
+    a = dict(_CSR, ldx=8, ldy=8, F=8, kind=1)
+    a.update(kw)
+    return L.gnn_spmm_csr_h16_f32(a["rowptr"], a["col"], a["val"], a["M"], a["K"], a["nnz"], a["X"], a["ldx"],
+                                  a["kind"], a["Y"], a["ldy"], a["F"], a["ws"], a["wsb"], a["unit"], None)
+
+
+def _call_graph_f32(L, **kw):
+    a = dict(_BLOCK, row0=0, rows=4, e0=0)
+    a.update(kw)
+    return L.gnn_spmm_graph_f32(a["indptr"], a["indices"], a["degree"], a["N"], a["row0"], a["rows"], a["e0"],
+                                a["nnz"], a["X"], a["ldx"], a["kind"], a["Y"], a["ldy"], a["F"], a["ws"], a["wsb"], None)
+
+
+def _call_rows_f32(L, **kw):
+    a = dict(_BLOCK, rows=_P, M=4, rowseg=_P, table=_P, K=64)
+    a.update(kw)
+    return L.gnn_spmm_rows_f32(a["indptr"], a["indices"], a["degree"], a["N"], a["rows"], a["M"], a["rowseg"],
+                               a["nnz"], a["table"], a["K"], a["X"], a["ldx"], a["kind"], a["Y"], a["ldy"], a["F"],
+                               a["ws"], a["wsb"], None, None)
+
+
+_H16 = dict(kind=1, F=8, ldx=8, ldy=8)  # a 16-bit call of the block entry points
+
+# (call, arguments that differ from the defaults, the entry point the message names, its distinguishing words)
+_REFUSED = [
+    # gnn_spmm_csr_f32 (a wrapper of _ex: its messages say gnn_spmm_csr_f32)
+    (_call_csr_f32, dict(M=-1), "gnn_spmm_csr_f32", "negative"),
+    (_call_csr_f32, dict(F=-1), "gnn_spmm_csr_f32", "negative"),
+    (_call_csr_f32, dict(M=1 << 31), "gnn_spmm_csr_f32", "2^31"),
+    (_call_csr_f32, dict(nnz=1 << 31), "gnn_spmm_csr_f32", "2^31"),
+    (_call_csr_f32, dict(ldx=8), "gnn_spmm_csr_f32", "F (12) > ldx (8)"),
+    (_call_csr_f32, dict(ldy=8), "gnn_spmm_csr_f32", "F (12) > ldy (8)"),
+    (_call_csr_f32, dict(rowptr=None), "gnn_spmm_csr_f32", "NULL rowptr/Y"),
+    (_call_csr_f32, dict(Y=None), "gnn_spmm_csr_f32", "NULL rowptr/Y"),
+    (_call_csr_f32, dict(col=None), "gnn_spmm_csr_f32", "NULL col/val/X"),
+    (_call_csr_f32, dict(X=None), "gnn_spmm_csr_f32", "NULL col/val/X"),
+    (_call_csr_f32, dict(ws=None), "gnn_spmm_csr_f32", "workspace too small (%d < 512)" % _BIG),
+    (_call_csr_f32, dict(wsb=511), "gnn_spmm_csr_f32", "workspace too small (511 < 512)"),
+    (_call_csr_f32, dict(ws=_P + 8), "gnn_spmm_csr_f32", "workspace not 16-byte aligned"),
+    # two failing conditions: the earlier check speaks
+    (_call_csr_f32, dict(M=-1, ldx=8), "gnn_spmm_csr_f32", "negative"),
+    (_call_csr_f32, dict(M=1 << 31, ldx=8), "gnn_spmm_csr_f32", "2^31"),
+    (_call_csr_f32, dict(ldx=8, ldy=8), "gnn_spmm_csr_f32", "> ldx"),
+    (_call_csr_f32, dict(ldy=8, Y=None), "gnn_spmm_csr_f32", "> ldy"),
+    (_call_csr_f32, dict(rowptr=None, X=None), "gnn_spmm_csr_f32", "NULL rowptr/Y"),
+    (_call_csr_f32, dict(X=None, ws=None), "gnn_spmm_csr_f32", "NULL col/val/X"),
+    (_call_csr_f32, dict(ws=_P + 8, wsb=0), "gnn_spmm_csr_f32", "workspace too small"),
+    # gnn_spmm_csr_f32_ex: the shared checks say gnn_spmm_csr_f32, the residual's own say _ex
+    (_call_csr_f32_ex, dict(K=-1), "gnn_spmm_csr_f32", "negative"),
+    (_call_csr_f32_ex, dict(K=1 << 31), "gnn_spmm_csr_f32", "2^31"),
+    (_call_csr_f32_ex, dict(ldx=8), "gnn_spmm_csr_f32", "F (12) > ldx (8)"),
+    (_call_csr_f32_ex, dict(ldy=8), "gnn_spmm_csr_f32", "F (12) > ldy (8)"),
+    (_call_csr_f32_ex, dict(val=None), "gnn_spmm_csr_f32", "NULL col/val/X"),
+    (_call_csr_f32_ex, dict(rmap=_P), "gnn_spmm_csr_f32_ex", "rmap needs R"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P, ldr=8), "gnn_spmm_csr_f32_ex", "rmap needs R"),
+    (_call_csr_f32_ex, dict(rmap=_P, X=None), "gnn_spmm_csr_f32", "NULL col/val/X"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P, ldr=12, wsb=8), "gnn_spmm_csr_f32", "workspace too small (8 < 512)"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P, ldr=12, ws=_P + 4), "gnn_spmm_csr_f32", "workspace not 16-byte aligned"),
+    # the residual's alignment for the vector width of the call (4 here): unit kernel, then row kernel
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P + 4, ldr=12), "gnn_spmm_csr_f32_ex", "R (ldr 12) not aligned for 4-wide"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P, ldr=14), "gnn_spmm_csr_f32_ex", "R (ldr 14) not aligned for 4-wide"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P + 4, ldr=12, ws=None), "gnn_spmm_csr_f32", "workspace too small"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P + 8, ldr=12, nnz=4, unit=0, ws=None), "gnn_spmm_csr_f32_ex",
+     "R (ldr 12) not aligned for 4-wide"),
+    (_call_csr_f32_ex, dict(rmap=_P, R=_P + 4, ldr=14, ldx=14, ldy=14, F=14, nnz=4, unit=0), "gnn_spmm_csr_f32_ex",
+     "R (ldr 14) not aligned for 2-wide"),
+    # gnn_spmm_csr_h16_f32
+    (_call_csr_h16_f32, dict(kind=0), "gnn_spmm_csr_h16_f32", "kind 0 is neither"),
+    (_call_csr_h16_f32, dict(kind=3), "gnn_spmm_csr_h16_f32", "kind 3 is neither"),
+    (_call_csr_h16_f32, dict(nnz=-1), "gnn_spmm_csr_h16_f32", "negative"),
+    (_call_csr_h16_f32, dict(K=1 << 31), "gnn_spmm_csr_h16_f32", "2^31"),
+    (_call_csr_h16_f32, dict(ldx=4), "gnn_spmm_csr_h16_f32", "F (8) > ldx (4)"),
+    (_call_csr_h16_f32, dict(ldx=4, K=0, nnz=0), "gnn_spmm_csr_h16_f32", "F (8) > ldx (4)"),  # no K == 0 exemption
+    (_call_csr_h16_f32, dict(ldy=4), "gnn_spmm_csr_h16_f32", "F (8) > ldy (4)"),
+    (_call_csr_h16_f32, dict(ldy=4, M=0), "gnn_spmm_csr_h16_f32", "F (8) > ldy (4)"),  # no M == 0 exemption
+    (_call_csr_h16_f32, dict(F=6), "gnn_spmm_csr_h16_f32", "must be multiples of 4"),
+    (_call_csr_h16_f32, dict(ldx=10), "gnn_spmm_csr_h16_f32", "must be multiples of 4"),
+    (_call_csr_h16_f32, dict(ldy=10), "gnn_spmm_csr_h16_f32", "must be multiples of 4"),
+    (_call_csr_h16_f32, dict(X=_P + 4), "gnn_spmm_csr_h16_f32", "X not 8-byte aligned"),
+    (_call_csr_h16_f32, dict(Y=_P + 8), "gnn_spmm_csr_h16_f32", "Y not 16-byte aligned"),
+    (_call_csr_h16_f32, dict(Y=_P + 8, M=0), "gnn_spmm_csr_h16_f32", "Y not 16-byte aligned"),  # before the early return
+    (_call_csr_h16_f32, dict(rowptr=None), "gnn_spmm_csr_h16_f32", "NULL rowptr/Y"),
+    (_call_csr_h16_f32, dict(X=None), "gnn_spmm_csr_h16_f32", "NULL col/val/X"),
+    (_call_csr_h16_f32, dict(ws=None), "gnn_spmm_csr_h16_f32", "workspace too small (%d < 256)" % _BIG),
+    (_call_csr_h16_f32, dict(wsb=255), "gnn_spmm_csr_h16_f32", "workspace too small (255 < 256)"),
+    (_call_csr_h16_f32, dict(ws=_P + 8), "gnn_spmm_csr_h16_f32", "workspace not 16-byte aligned"),
+    (_call_csr_h16_f32, dict(kind=0, M=-1), "gnn_spmm_csr_h16_f32", "kind 0 is neither"),
+    (_call_csr_h16_f32, dict(M=-1, ldx=4), "gnn_spmm_csr_h16_f32", "negative"),
+    (_call_csr_h16_f32, dict(ldx=4, ldy=4), "gnn_spmm_csr_h16_f32", "> ldx"),
+    (_call_csr_h16_f32, dict(F=6, X=_P + 4), "gnn_spmm_csr_h16_f32", "must be multiples of 4"),
+    (_call_csr_h16_f32, dict(X=_P + 4, Y=_P + 8), "gnn_spmm_csr_h16_f32", "X not 8-byte aligned"),
+    (_call_csr_h16_f32, dict(Y=_P + 8, rowptr=None), "gnn_spmm_csr_h16_f32", "Y not 16-byte aligned"),
+    # gnn_spmm_graph_f32
+    (_call_graph_f32, dict(kind=3), "gnn_spmm_graph_f32", "kind 3 is none of"),
+    (_call_graph_f32, dict(rows=-1), "gnn_spmm_graph_f32", "negative"),
+    (_call_graph_f32, dict(e0=-1), "gnn_spmm_graph_f32", "negative"),
+    (_call_graph_f32, dict(rows=1 << 31), "gnn_spmm_graph_f32", "2^31"),
+    (_call_graph_f32, dict(N=1 << 31), "gnn_spmm_graph_f32", "2^31"),
+    (_call_graph_f32, dict(row0=61), "gnn_spmm_graph_f32", "row0 (61) + rows (4) > num_nodes (64)"),
+    (_call_graph_f32, dict(ldx=8), "gnn_spmm_graph_f32", "F (12) > ldx (8)"),
+    (_call_graph_f32, dict(ldy=8), "gnn_spmm_graph_f32", "F (12) > ldy (8)"),
+    (_call_graph_f32, dict(_H16, F=6), "gnn_spmm_graph_f32", "must be multiples of 4"),
+    (_call_graph_f32, dict(_H16, kind=2, ldx=10), "gnn_spmm_graph_f32", "must be multiples of 4"),
+    (_call_graph_f32, dict(_H16, X=_P + 4), "gnn_spmm_graph_f32", "X not 8-byte aligned"),
+    (_call_graph_f32, dict(_H16, Y=_P + 8), "gnn_spmm_graph_f32", "Y not 16-byte aligned"),
+    (_call_graph_f32, dict(ws=None), "gnn_spmm_graph_f32", "workspace too small (0 < "),
+    (_call_graph_f32, dict(wsb=4096), "gnn_spmm_graph_f32", "workspace too small (4096 < "),
+    (_call_graph_f32, dict(ws=_P + 8), "gnn_spmm_graph_f32", "workspace not 16-byte aligned"),
+    (_call_graph_f32, dict(indptr=None), "gnn_spmm_graph_f32", "NULL indptr/degree/Y"),
+    (_call_graph_f32, dict(Y=None), "gnn_spmm_graph_f32", "NULL indptr/degree/Y"),
+    (_call_graph_f32, dict(indices=None), "gnn_spmm_graph_f32", "NULL indices/X"),
+    (_call_graph_f32, dict(X=None), "gnn_spmm_graph_f32", "NULL indices/X"),
+    (_call_graph_f32, dict(kind=3, rows=-1), "gnn_spmm_graph_f32", "kind 3 is none of"),
+    (_call_graph_f32, dict(rows=-1, ldx=8), "gnn_spmm_graph_f32", "negative"),
+    (_call_graph_f32, dict(row0=61, ldx=8), "gnn_spmm_graph_f32", "> num_nodes"),
+    (_call_graph_f32, dict(ldx=8, ldy=8), "gnn_spmm_graph_f32", "> ldx"),
+    (_call_graph_f32, dict(_H16, ldy=4, Y=_P + 8), "gnn_spmm_graph_f32", "> ldy"),
+    (_call_graph_f32, dict(_H16, Y=_P + 8, ws=None), "gnn_spmm_graph_f32", "Y not 16-byte aligned"),
+    (_call_graph_f32, dict(ws=None, indptr=None), "gnn_spmm_graph_f32", "workspace too small"),
+    (_call_graph_f32, dict(ws=None, rows=0), "gnn_spmm_graph_f32", "workspace too small"),  # before the early return
+    # gnn_spmm_rows_f32
+    (_call_rows_f32, dict(kind=-1), "gnn_spmm_rows_f32", "kind -1 is none of"),
+    (_call_rows_f32, dict(M=-1), "gnn_spmm_rows_f32", "negative"),
+    (_call_rows_f32, dict(K=-1), "gnn_spmm_rows_f32", "negative"),
+    (_call_rows_f32, dict(M=1 << 31), "gnn_spmm_rows_f32", "2^31"),
+    (_call_rows_f32, dict(nnz=1 << 31), "gnn_spmm_rows_f32", "2^31"),
+    (_call_rows_f32, dict(K=65), "gnn_spmm_rows_f32", "K (65) > num_nodes (64)"),
+    (_call_rows_f32, dict(ldx=8), "gnn_spmm_rows_f32", "F (12) > ldx (8)"),
+    (_call_rows_f32, dict(ldy=8), "gnn_spmm_rows_f32", "F (12) > ldy (8)"),
+    (_call_rows_f32, dict(_H16, F=6), "gnn_spmm_rows_f32", "must be multiples of 4"),
+    (_call_rows_f32, dict(_H16, kind=2, ldy=10), "gnn_spmm_rows_f32", "must be multiples of 4"),
+    (_call_rows_f32, dict(_H16, X=_P + 4), "gnn_spmm_rows_f32", "X not 8-byte aligned"),
+    (_call_rows_f32, dict(_H16, Y=_P + 8), "gnn_spmm_rows_f32", "Y not 16-byte aligned"),
+    (_call_rows_f32, dict(ws=None), "gnn_spmm_rows_f32", "workspace too small (0 < "),
+    (_call_rows_f32, dict(wsb=1024), "gnn_spmm_rows_f32", "workspace too small (1024 < "),
+    (_call_rows_f32, dict(ws=_P + 8), "gnn_spmm_rows_f32", "workspace not 16-byte aligned"),
+    (_call_rows_f32, dict(rowseg=None), "gnn_spmm_rows_f32", "NULL indptr/degree/rows/rowseg/Y"),
+    (_call_rows_f32, dict(table=None), "gnn_spmm_rows_f32", "NULL or misaligned table"),
+    (_call_rows_f32, dict(table=_P + 4), "gnn_spmm_rows_f32", "NULL or misaligned table"),
+    (_call_rows_f32, dict(indices=None), "gnn_spmm_rows_f32", "NULL indices/X"),
+    (_call_rows_f32, dict(X=None), "gnn_spmm_rows_f32", "NULL indices/X"),
+    (_call_rows_f32, dict(kind=-1, M=-1), "gnn_spmm_rows_f32", "kind -1 is none of"),
+    (_call_rows_f32, dict(M=1 << 31, K=65), "gnn_spmm_rows_f32", "2^31"),
+    (_call_rows_f32, dict(K=65, ldx=8), "gnn_spmm_rows_f32", "> num_nodes"),
+    (_call_rows_f32, dict(ldx=8, ldy=8), "gnn_spmm_rows_f32", "> ldx"),
+    (_call_rows_f32, dict(_H16, X=_P + 4, Y=_P + 8), "gnn_spmm_rows_f32", "X not 8-byte aligned"),
+    (_call_rows_f32, dict(ws=_P + 8, wsb=0), "gnn_spmm_rows_f32", "workspace too small"),
+    (_call_rows_f32, dict(rowseg=None, table=None), "gnn_spmm_rows_f32", "NULL indptr/degree/rows/rowseg/Y"),
+    (_call_rows_f32, dict(table=None, X=None), "gnn_spmm_rows_f32", "NULL or misaligned table"),
+]
+
+_NONE = dict(rowptr=None, col=None, val=None, X=None, Y=None, ws=None, wsb=0)
+_NONE_BLOCK = dict(indptr=None, indices=None, degree=None, X=None, Y=None)  # the workspace is checked first
+# calls that return 0 before the NULL checks: an empty output (M == 0 or F == 0)
+_EMPTY = [
+    (_call_csr_f32, dict(_NONE, M=0)),
+    (_call_csr_f32, dict(_NONE, F=0)),
+    (_call_csr_f32, dict(_NONE, M=0, ldy=0)),  # F <= ldy is not asked of an empty output
+    (_call_csr_f32, dict(_NONE, K=0, nnz=0, ldx=0, M=0)),  # nor F <= ldx of an empty X
+    (_call_csr_f32_ex, dict(_NONE, M=0, rmap=_P)),  # before the residual's checks too
+    (_call_csr_f32_ex, dict(_NONE, F=0)),
+    (_call_csr_h16_f32, dict(_NONE, M=0)),
+    (_call_csr_h16_f32, dict(_NONE, F=0)),
+    (_call_graph_f32, dict(_NONE_BLOCK, rows=0, nnz=0)),
+    (_call_graph_f32, dict(_NONE_BLOCK, F=0)),
+    (_call_graph_f32, dict(_NONE_BLOCK, rows=0, nnz=0, **_H16)),
+    (_call_rows_f32, dict(_NONE_BLOCK, rows=None, rowseg=None, table=None, M=0, nnz=0)),
+    (_call_rows_f32, dict(_NONE_BLOCK, rows=None, rowseg=None, table=None, F=0)),
+    (_call_rows_f32, dict(_NONE_BLOCK, rows=None, rowseg=None, table=None, M=0, nnz=0, **_H16)),
+]
+
+
+def _spmm_env_cleared(monkeypatch):
+    for k in ("GNN_SPMM_ROWK", "GNN_SPMM_ROWK_WPR", "GNN_SPMM_G", "GNN_SPMM_NJ", "GNN_SPMM_VW", "GNN_SPMM_XCD",
+              "GNN_SPMM_SMALL_U16", "GNN_SPMM_CROWS"):
+        monkeypatch.delenv(k, raising=False)
+
+
+@pytest.mark.parametrize("call,args,name,words", _REFUSED,
+                         ids=["%s-%d" % (c[0].__name__[6:], i) for i, c in enumerate(_REFUSED)])
+def test_spmm_refusals(monkeypatch, call, args, name, words):
+    """Each aggregation entry point refuses a bad call with -22 and a message that opens with the entry
+    point's name and holds the words of the failed check; of two failed checks the earlier one speaks."""
+    _spmm_env_cleared(monkeypatch)
+    L = _lib.lib()
+    L.gnn_gather_rows_f32(None, 1, None, None, 1, None, -5, 1, None)  # some other message first
+    assert call(L, **args) == -22
+    msg = L.gnn_last_error().decode()
+    assert msg.startswith(name + ": "), msg
+    assert words in msg, msg
+
+
+@pytest.mark.parametrize("call,args", _EMPTY, ids=["%s-%d" % (c[0].__name__[6:], i) for i, c in enumerate(_EMPTY)])
+def test_spmm_empty_calls_return_before_null_checks(monkeypatch, call, args):
+    _spmm_env_cleared(monkeypatch)
+    assert call(_lib.lib(), **args) == 0
+
+
 def test_workspace_and_config():
     from gnn_amd.custom_sparse_ops import spmm_config
 

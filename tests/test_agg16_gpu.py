@@ -327,6 +327,59 @@ def test_deterministic_and_timed(dev, dtype):
     assert r16[1] > 0 and r32[1] > 0
 
 
+@pytest.mark.parametrize("timed", [False, True], ids=["plain", "timed"])
+@pytest.mark.parametrize("unit,stem", [(0, "spmm_row"), (16, "spmm_unit"), (64, "spmm_unit")],
+                         ids=["row", "cut", "whole"])
+def test_every_launch_form_on_the_smallest_operand(dev, monkeypatch, unit, stem, timed):
+    """Each launch the aggregation's host path can make, on the smallest operand that reaches it —
+    4 rows of 0, 1, 16 and 40 entries over K = 64: the row kernel (forced on, unit_nnz 0), the unit
+    kernel with the 40-entry row cut and combined (unit_nnz 16) and as one unit with nothing to
+    combine (64) — for fp32 X without and with a residual (F = 12) and for fp16 / bf16 X (F = 8), with
+    and without armed timing events. 16-bit equals fp32 on the widened X bit for bit; every result
+    is the oracle's within the file's tolerance; a timed launch records the kernel it ran."""
+    monkeypatch.setenv("GNN_SPMM_ROWK", "1" if unit == 0 else "0")
+    M, K = 4, 64
+    rng = np.random.default_rng(7)
+    full, rowptr, col, nf = random_csr(M, K, np.array([0, 1, 16, 40]), rng)
+    op = _op(dev, full, rowptr, col, nf, M, K)
+    ocol, oval = O.build_operand(full, rowptr, col, nf)
+    g = torch.Generator().manual_seed(11)
+    Xf = torch.randn(K, 12, generator=g).to(dev)
+    R = torch.randn(3, 12, generator=g).to(dev)
+    rmap = torch.tensor([2, -1, 0, 1], dtype=torch.int32, device=dev)
+    cso.enable_timing(timed)
+    try:
+        cso.take_timing_records()
+        Yp = cso.spmm_csr(op, Xf, unit_nnz=unit)
+        Yr = cso.spmm_csr(op, Xf, unit_nnz=unit, residual=R, rmap=rmap)
+        h16 = []
+        for dtype in DTYPES:
+            X16, X32 = _x16(dev, K, 8, dtype, 3)
+            h16.append((cso.spmm_csr(op, X16, unit_nnz=unit), cso.spmm_csr(op, X32, unit_nnz=unit), X32))
+        recs = cso.take_timing_records()
+    finally:
+        cso.enable_timing(False)
+    torch.cuda.synchronize()
+    ref = O.spmm_f32(rowptr, ocol, oval, np.ascontiguousarray(Xf.cpu().numpy()))
+    np.testing.assert_allclose(Yp.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    want = ref.copy()
+    m = rmap.cpu().numpy()
+    want[m >= 0] += R.cpu().numpy()[m[m >= 0]]
+    np.testing.assert_allclose(Yr.cpu().numpy(), want, rtol=RTOL, atol=ATOL)
+    for a, b, X32 in h16:
+        assert torch.equal(_i32(a), _i32(b))
+        ref16 = O.spmm_f32(rowptr, ocol, oval, np.ascontiguousarray(X32.cpu().numpy()))
+        np.testing.assert_allclose(a.cpu().numpy(), ref16, rtol=RTOL, atol=ATOL)
+    assert len(recs) == (6 if timed else 0)
+    if timed:
+        names = [r[3] for r in recs]
+        assert names[0].startswith(stem + "_kernel<4, ") and names[0].endswith(", false>")
+        assert names[1] == names[0].replace("false", "true")
+        assert names[2].startswith(stem + "16_kernel<1, ") and names[4].startswith(stem + "16_kernel<2, ")
+        assert names[3] == names[5] == names[0]
+        assert all(r[1] > 0 for r in recs)
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_spmm_autograd_forwards_16bit(dev, dtype):
     """SparseDenseMM takes a 16-bit mat2 (fp32 out) and produces no gradient for it."""
