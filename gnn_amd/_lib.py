@@ -56,6 +56,13 @@ _SIGNATURES = {
     "gnn_nbr_draw": (_INT, [_VP, _VP, _I64, _I64, _VP, _I64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, _VP, _VP,
                             _VP, _I64, _VP, _VP]),
     "gnn_nbr_relabel": (_INT, [_VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "gnn_lw_race": (_INT, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, ctypes.c_uint64, ctypes.c_int32, _VP, _VP, _I64, _VP,
+                           _VP, _VP]),
+    "gnn_lw_select_workspace_bytes": (_SZ, []),
+    "gnn_lw_select": (_INT, [_VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "gnn_lw_finish_workspace_bytes": (_SZ, [_I64, _I64]),
+    "gnn_lw_finish": (_INT, [_VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP,
+                             _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

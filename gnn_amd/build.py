@@ -11,9 +11,9 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("spmm.hip", "operand.hip", "gather.hip", "runtime.hip", "sage.hip", "gemm.hip", "optim.hip", "head.hip", "extract.hip", "step.hip", "colcount.hip", "stage.hip", "closure.hip", "neighbor.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("spmm.hip", "operand.hip", "gather.hip", "runtime.hip", "sage.hip", "gemm.hip", "optim.hip", "head.hip", "extract.hip", "step.hip", "colcount.hip", "stage.hip", "closure.hip", "neighbor.hip", "layerwise.hip")]
 HDRS = [os.path.join(REPO, "include", f) for f in ("gnn_spmm.h", "gnn_layers.h", "gnn_optim.h", "gnn_extract.h", "gnn_step.h", "gnn_stage.h")] + [
-    os.path.join(HERE, "csrc", f) for f in ("common.h", "spmm_device.h", "spmm_unit_body.inc", "spmm_row_body.inc")]
+    os.path.join(HERE, "csrc", f) for f in ("common.h", "spmm_device.h", "graph_rows.h", "spmm_unit_body.inc", "spmm_row_body.inc")]
 OUT = os.path.join(HERE, "libgnn_spmm.so")
 ARCH = os.environ.get("GNN_OFFLOAD_ARCH", "gfx950")
 

@@ -37,11 +37,13 @@
 
 #include "common.h"
 #include "gnn_extract.h"
+#include "graph_rows.h"
 
 namespace {
 
 using gnn::align_up;
 using gnn::ceil_div;
+using gnn::row_span;
 
 using Word = uint2;  // extract.hip's membership word
 constexpr int NB_ITEMS = 8;
@@ -57,20 +59,6 @@ __host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // sage.hip's 
   x *= 0x846ca68bu;
   x ^= x >> 16;
   return x;
-}
-
-// The graph row of node r: its first entry and its degree. False (and d = 0) for a node outside
-// the graph or a row pointer that would put a read outside [0, E).
-__device__ __forceinline__ bool row_span(const int64_t* __restrict__ indptr, int N, int64_t E, int r, int64_t& b,
-                                         int& d) {
-  b = 0;
-  d = 0;
-  if ((unsigned)r >= (unsigned)N) return false;
-  const int64_t b0 = indptr[r], e0 = indptr[r + 1];
-  if (b0 < 0 || e0 < b0 || e0 > E || e0 - b0 >= (int64_t)INT_MAX) return false;
-  b = b0;
-  d = (int)(e0 - b0);
-  return true;
 }
 
 // rowptr of workgroup j's rows = the exclusive scan of their k within the chunk; csum[j] = the

@@ -1,0 +1,336 @@
+"""Layer-wise importance sampling (LADIES) drawn on the device: a hashed race over the resident graph.
+
+The host samplers (``loader.KINDS``) draw a layer with ``np.random.choice(N, s_num, p = pi / sum(pi),
+replace=False)``, pi = the entry count per column of U = lap[rows, :]: successive sampling without
+replacement, proportional to integer weights. The same law comes from a race: give every entry of U
+an independent uniform value and every column the maximum over its entries. The overall maximum is
+equally likely to be any entry, so column j leads with probability pi_j / sum(pi); removing it
+leaves the same situation among the rest. The ``s_num`` columns with the largest maxima are
+distributed exactly as ``np.random.choice``'s set. It is another random stream than the host
+samplers' MT19937 draw: like FastGCN's its parity is unpinned, its law is pinned.
+
+The values are a hash of (column node id, row position) under a key of (seed, layer), in 64-bit
+unsigned arithmetic (include/gnn_extract.h states the draw in full):
+  mix64 = the splitmix64 finaliser;  K = mix64(seed + (layer + 1) * 0x9E3779B97F4A7C15);
+  h(i, c) = mix64((c << 32 | i) + K) for the entry in row position i and column node id c;
+  key[c] = max_i h(i, c), count[c] = the number of entries.
+mix64 is a bijection, so all keys are distinct and no tie rule exists. ``race_keys`` restates it in
+numpy, ``ladies_race_host`` builds the whole batch there (the GPU tests' oracle and the source of
+``device="cpu"``), ``LayerwiseSampler.sample`` builds the same batch on the GPU, array for array.
+``layer`` is the model's layer index (0 = the bottom layer, as ``adjs``).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import custom_sparse_ops as cso
+from .neighbor import HostNeighborBatch, NeighborBatch, ResidentSampler, _batch_ids, batch_seed  # noqa: F401
+from .sampler import native_graph
+
+_MASK = 0xFFFFFFFFFFFFFFFF
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def mix64(z) -> np.ndarray:
+    """The splitmix64 finaliser over uint64 (arrays or scalars), mod 2^64."""
+    z = np.array(z, dtype=np.uint64, copy=True)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return z
+
+
+def race_key(seed, layer: int) -> np.ndarray:
+    """K = mix64(seed + (layer + 1) * 0x9E3779B97F4A7C15), uint64; ``seed`` may be an array."""
+    step = np.uint64(((int(layer) + 1) * _GOLDEN) & _MASK)
+    s = np.uint64(int(seed) & _MASK) if np.ndim(seed) == 0 else np.asarray(seed).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        return mix64(s + step)
+
+
+def _entries(indptr: np.ndarray, indices: np.ndarray, rows: np.ndarray):
+    """U = lap[rows, :] entry by entry, in row order: (row position int64, column id int64, deg int64[M])."""
+    start = indptr[rows]
+    deg = (indptr[rows + 1] - start).astype(np.int64)
+    first = np.concatenate([[0], np.cumsum(deg)])[:-1]
+    i = np.repeat(np.arange(rows.size, dtype=np.int64), deg)
+    ent = np.arange(int(deg.sum()), dtype=np.int64) - np.repeat(first, deg) + np.repeat(start, deg)
+    return i, indices[ent].astype(np.int64), deg
+
+
+def entry_values(seed: int, layer: int, i, c) -> np.ndarray:
+    """h(i, c) = mix64((c << 32 | i) + K) of entries in row positions ``i`` and columns ``c``, uint64."""
+    i, c = np.asarray(i).astype(np.uint64), np.asarray(c).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        return mix64(((c << np.uint64(32)) | (i & np.uint64(0xFFFFFFFF))) + race_key(seed, layer))
+
+
+def _column_max(N: int, i: np.ndarray, c: np.ndarray, h: np.ndarray):
+    counts = np.bincount(c, minlength=N).astype(np.int64)
+    keys = np.zeros(N, dtype=np.uint64)
+    if c.size:
+        o = np.lexsort((h, c))
+        last = np.concatenate([c[o][1:] != c[o][:-1], [True]])
+        keys[c[o][last]] = h[o][last]
+    return counts, keys
+
+
+def race_keys(seed: int, layer: int, indptr, indices, rows):
+    """(counts int64[N], keys uint64[N]) of U = lap[rows, :]: the entries and the largest entry
+    value per column node (key 0 where the count is 0)."""
+    indptr, indices = np.asarray(indptr), np.asarray(indices)
+    i, c, _ = _entries(indptr, indices, np.asarray(rows, dtype=np.int64).reshape(-1))
+    return _column_max(indptr.size - 1, i, c, entry_values(seed, layer, i, c))
+
+
+def race_select(counts: np.ndarray, keys: np.ndarray, samp_num: int):
+    """(s_num, selected): the s_num = min(live columns, samp_num) live columns with the largest keys."""
+    live = np.flatnonzero(counts)
+    s_num = min(int(live.size), int(samp_num))
+    if s_num == 0:
+        return 0, np.zeros(0, dtype=np.int64)
+    part = np.argpartition(keys[live], live.size - s_num)[live.size - s_num:]
+    return s_num, np.sort(live[part]).astype(np.int64)
+
+
+def race_normfact(counts: np.ndarray, after: np.ndarray, s_num: int) -> np.ndarray:
+    """sampler.py:137, float32: 1 / float32(clip(s_num * p[after], 1e-10, 1)) with p = counts /
+    sum(counts) in float64 (the reciprocal is a float32 division; p counts as 0 when nothing was
+    counted, where the reference would have divided by zero)."""
+    total = int(counts.sum())
+    p = counts[after] / total if total > 0 else np.zeros(after.size)
+    return 1 / np.clip(s_num * p, 1e-10, 1).astype(np.float32)
+
+
+@dataclass
+class HostLayerwiseBatch(HostNeighborBatch):
+    """``ladies_race_host``'s result: ``HostNeighborBatch`` plus, per aggregating layer, the draw's
+    ``s_num`` and ``normfact`` (float32 over ``sets[l]``); None for an order-0 layer."""
+    s_num: list = field(default_factory=list)
+    normfact: list = field(default_factory=list)
+
+
+def _samp_list(samp_num, orders) -> List[Optional[int]]:
+    """One sample size per layer, bottom-up (None for an order-0 layer), from one int or the
+    reference's ``samp_num_list`` (indexed top-down over all layers, sampler.py:125)."""
+    orders = [int(o) for o in orders]
+    if not orders or any(o not in (0, 1) for o in orders):
+        raise ValueError(f"layer-wise sampling: orders must be a non-empty list of 0 / 1, got {orders}")
+    L = len(orders)
+    sl = [int(samp_num)] * L if np.ndim(samp_num) == 0 else [int(s) for s in samp_num]
+    if len(sl) < L:
+        raise ValueError(f"layer-wise sampling: {len(sl)} sample sizes for {L} layers (one per layer, top-down)")
+    out = [sl[L - 1 - l] if orders[l] else None for l in range(L)]
+    if any(s is not None and not 1 <= s < 2**31 for s in out):
+        raise ValueError(f"layer-wise sampling: sample sizes must lie in [1, 2^31), got {sl}")
+    return out
+
+
+def _graph_of(lap):
+    g = native_graph(lap)
+    if g.data is not None:
+        raise ValueError("layer-wise sampling: the graph stores values of its own (explicit zeros among its "
+                         "entries); weighted graphs are out of scope of the device draw")
+    return g
+
+
+def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequence[int]) -> HostLayerwiseBatch:
+    """The whole batch in numpy: per layer (bottom-up, as ``adjs``) the operand pieces (rowptr, col,
+    val, shape) of adj = lap[rows, :][:, after] with create_coo_tensor's values, the positions of
+    the rows in ``after`` and the layer-0 input nodes. ``samp_num_list``: one int, or the
+    reference's list (one per layer, top-down); ``lap`` a scipy matrix or a sampler.NativeGraph
+    without stored values."""
+    g = _graph_of(lap)
+    sl = _samp_list(samp_num_list, orders)
+    L = len(sl)
+    N = g.num_nodes
+    rows = _batch_ids(batch_nodes, N)
+    layers, sampled, sets = [None] * L, [np.zeros(0, np.int64)] * L, [None] * (L + 1)
+    s_nums, nfs = [None] * L, [None] * L
+    sets[L] = rows
+    for l in range(L - 1, -1, -1):
+        if sl[l] is None:
+            sets[l] = rows
+            continue
+        i, c, deg = _entries(g.indptr, g.indices, rows)
+        counts, keys = _column_max(N, i, c, entry_values(seed, l, i, c))
+        s_num, selected = race_select(counts, keys, sl[l])
+        after = np.unique(np.concatenate([selected, rows]))
+        nf = race_normfact(counts, after, s_num)
+        K = int(after.size)
+        pos = np.minimum(np.searchsorted(after, c), K - 1) if K else np.zeros(0, np.int64)
+        keep = after[pos] == c if K else np.zeros(0, bool)
+        rowptr = np.concatenate([[0], np.cumsum(np.bincount(i[keep], minlength=rows.size))]).astype(np.int32)
+        col = pos[keep].astype(np.int32)
+        with np.errstate(divide="ignore"):
+            val = ((1.0 / deg.astype(np.float64))[i[keep]] * nf.astype(np.float64)[col]).astype(np.float32)
+        layers[l] = (rowptr, col, val, (int(rows.size), K))
+        sampled[l] = np.searchsorted(after, rows).astype(np.int64)
+        s_nums[l], nfs[l] = s_num, nf
+        sets[l] = rows = after
+    return HostLayerwiseBatch(layers, sampled, sets[0], sets, s_nums, nfs)
+
+
+class LayerwiseSampler(ResidentSampler):
+    """LADIES batches of ``lap`` for a model with layer ``orders`` (0 / 1, bottom-up), drawn by the
+    race over the resident graph.
+
+    ``samp_num``: one int, or the reference's ``samp_num_list`` (one per layer, top-down).
+    ``feats`` / ``labels_full`` / ``device`` and the methods ``sample`` / ``epoch`` / ``sequential``
+    as ``neighbor.NeighborSampler``: the feature table lives on the device, batch b of a pass draws
+    under ``batch_seed(seed, b)``.
+
+    On a GPU ``sample`` runs, per aggregating layer on the current stream, gnn_closure_mark over the
+    rows with expand (the live table: the rows and their columns), gnn_closure_list, gnn_lw_race,
+    gnn_lw_select, gnn_closure_mark over rows ++ selected ids, gnn_closure_list, gnn_lw_finish, then ONE
+    device-to-host read of (K, nnz, the transposed segments' total, the next layer's segment total,
+    error flags), then ``custom_sparse_ops.extract_operand`` (gnn_ladies_extract_f32) and
+    gnn_closure_rank; buffers are sized before the read by the host-known bounds min(N, M + sum of
+    deg(rows)) and M + samp_num. Below the top layer the rows are unique and ascending, so the
+    extraction builds the transpose too; the top layer (the caller's order, repeats allowed) gets
+    it from ``CsrOperand.transpose()`` and its row map only for unique batch nodes. The extraction
+    raises the graph's flag if its kept entries disagree with the race's counts: the flag is part of
+    the next layer's read, and of one last read per batch. With ``device="cpu"`` the same batches
+    come from ``ladies_race_host`` as torch COO operands.
+
+    Out of scope, refused: weighted graphs, scale_factor > 1, FastGCN, subgraph sampling, rank
+    splitting; ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
+
+    def __init__(self, lap, samp_num, orders, feats: torch.Tensor, labels_full, device, scale_factor: float = 1.0):
+        if scale_factor > 1:
+            raise ValueError("LayerwiseSampler: scale_factor > 1 (locality-skewed weights) is out of scope of "
+                             "the device draw")
+        self.graph = _graph_of(lap)
+        self.samp_nums = _samp_list(samp_num, orders)
+        self._setup(orders, feats, labels_full, device)
+        # a list here receives (layer, stage, event) after every stage of the device draw: the
+        # per-kernel split of scripts/layerwise_probe.py (timing events; off by default)
+        self.trace: Optional[list] = None
+
+    def _mark(self, layer: int, stage: str) -> None:
+        if self.trace is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.trace.append((layer, stage, ev))
+
+    def sample(self, batch_nodes, seed: int) -> NeighborBatch:
+        """The batch of ``batch_nodes`` (integer node ids, any order) under the draw seed ``seed``."""
+        q = _batch_ids(batch_nodes, self.N)
+        seed = int(seed) & _MASK
+        if not self.native:
+            return self._sample_cpu(q, seed)
+        from . import _lib
+
+        dev, N, dg = self.device, self.N, self.dgraph
+        Lb = _lib.lib()
+        nl = len(self.orders)
+        adjs: list = [None] * nl
+        sampled: list = [None] * nl
+        unique_top = np.unique(q).size == q.size
+        hp = dg.host_indptr
+        with _lib.on_device(dev):
+            st = _lib.stream_of(dev)
+            E, Et = int(dg.indices.numel()), int(dg.indices_t.numel())
+            rows = torch.from_numpy(q.astype(np.int32)).to(dev)
+            rowseg_total = int((hp[q + 1] - hp[q]).sum())  # the top layer's: host data
+            empty = torch.zeros(0, dtype=torch.int64, device=dev)
+            top = True
+            p = lambda t: t.data_ptr() if t.numel() else None
+            for l in range(nl - 1, -1, -1):
+                samp = self.samp_nums[l]
+                if samp is None:
+                    sampled[l] = empty
+                    continue
+                M = int(rows.numel())
+                if rowseg_total >= 2**31 or 2 * M + rowseg_total >= 2**31:
+                    raise RuntimeError(f"LayerwiseSampler: layer {l} spans {rowseg_total} graph entries (>= 2^31)")
+                cap = min(N, M + rowseg_total)     # >= the rows and their columns: the live table
+                kcap = min(N, M + min(cap, samp))  # >= |after|
+                # |live table|, sum(count), s_num, tau, K, nnz, colseg total, next rowseg total, (flag, the
+                # extractions' flag): words 4 .. 8 are the layer's one device-to-host read
+                word = torch.zeros(9, dtype=torch.int64, device=dev)
+                err = word[8:].view(torch.int32)
+                wsb = max(Lb.gnn_closure_workspace_bytes(N), Lb.gnn_lw_select_workspace_bytes(),
+                          Lb.gnn_lw_finish_workspace_bytes(M, kcap))
+                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+                tbytes = Lb.gnn_closure_table_bytes(N)
+                live = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+                table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+                live_ids = torch.empty(cap, dtype=torch.int32, device=dev)
+                count = torch.empty(cap, dtype=torch.int32, device=dev)
+                key = torch.empty(cap, dtype=torch.int64, device=dev)
+                seeds = torch.empty(M + cap, dtype=torch.int32, device=dev)  # rows ++ selected ids (or -1)
+                seeds[:M] = rows
+                ids = seeds[M:]
+                after = torch.empty(kcap, dtype=torch.int32, device=dev)
+                normfact = torch.empty(kcap, dtype=torch.float32, device=dev)
+                colptr = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
+                colseg = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
+                rowseg = torch.empty(M + 1, dtype=torch.int32, device=dev)
+                self._mark(l, "begin")
+                _lib.check(Lb.gnn_closure_mark(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, p(rows), M, 1,
+                                               live.data_ptr(), word[0:].data_ptr(), ws.data_ptr(), wsb, st),
+                           "gnn_closure_mark")
+                _lib.check(Lb.gnn_closure_list(live.data_ptr(), N, p(live_ids), cap, st), "gnn_closure_list")
+                self._mark(l, "mark_live+list")
+                _lib.check(Lb.gnn_lw_race(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, E, p(rows), M,
+                                          live.data_ptr(), seed, l, p(count), p(key), cap, word[1:].data_ptr(),
+                                          err.data_ptr(), st), "gnn_lw_race")
+                self._mark(l, "race")
+                _lib.check(Lb.gnn_lw_select(p(key), p(count), word[0:].data_ptr(), cap, samp, p(live_ids), p(ids),
+                                            word[2:].data_ptr(), word[3:].data_ptr(), ws.data_ptr(), wsb, st),
+                           "gnn_lw_select")
+                self._mark(l, "select")
+                _lib.check(Lb.gnn_closure_mark(None, None, N, p(seeds), M + cap, 0, table.data_ptr(),
+                                               word[4:].data_ptr(), ws.data_ptr(), wsb, st), "gnn_closure_mark")
+                _lib.check(Lb.gnn_closure_list(table.data_ptr(), N, p(after), kcap, st), "gnn_closure_list")
+                self._mark(l, "mark_after+list")
+                _lib.check(Lb.gnn_lw_finish(dg.indptr.data_ptr(), E, dg.indptr_t.data_ptr(), Et, N, p(rows), M,
+                                            p(after), word[4:].data_ptr(), kcap, live.data_ptr(), p(count), cap,
+                                            word[1:].data_ptr(), word[2:].data_ptr(), p(normfact), colptr.data_ptr(),
+                                            rowseg.data_ptr(), colseg.data_ptr(), word[5:].data_ptr(), ws.data_ptr(),
+                                            wsb, err.data_ptr(), st), "gnn_lw_finish")
+                self._mark(l, "finish")
+                err[1:2].copy_(dg.err)  # the extractions so far (the layer above's among them)
+                K, nnz, colseg_total, next_total, flags = (int(v) for v in word[4:].tolist())
+                if flags & 0xFFFFFFFF:
+                    raise RuntimeError(f"LayerwiseSampler: the device draw of layer {l} met a row or column outside "
+                                       "the graph or a total >= 2^31 (the resident graph does not match its row pointer)")
+                if flags >> 32:
+                    dg.check()
+                after = after[:K]
+                tr = l >= 1 and not top  # unique ascending rows: the extraction builds the transpose as well
+                op = cso.extract_operand(dg, rows, after, normfact[:K], nnz, rowseg,
+                                         colseg[: K + 1] if tr else None, colptr[: K + 1] if tr else None,
+                                         rowseg_total=rowseg_total, colseg_total=colseg_total if tr else None)
+                sn = cso.closure_rank(table, N, rows)
+                if l >= 1:  # the top layer's transpose is made here; below it is in place already
+                    self._top_maps(op, sn, M, K, unique_top or not top)
+                adjs[l], sampled[l] = op, sn
+                self._mark(l, "read+extract+rank+maps")
+                rows, rowseg_total, top = after, next_total, False
+            dg.check()  # the last extraction's flag
+            input_nodes = rows.long()
+            x0 = self._x0(input_nodes)
+        return NeighborBatch(x0, adjs, sampled, self._labels(q), input_nodes, q, seed)
+
+    def _sample_cpu(self, q: np.ndarray, seed: int) -> NeighborBatch:
+        hb = ladies_race_host(seed, q, [s or 1 for s in self.samp_nums[::-1]], self.graph, self.orders)  # top-down
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+        adjs = []
+        for lay in hb.layers:
+            if lay is None:
+                adjs.append(None)
+                continue
+            rowptr, col, val, (M, K) = lay
+            r = np.repeat(np.arange(M, dtype=np.int64), np.diff(rowptr))
+            # create_coo_tensor's CPU branch: the same values, coalesced
+            adjs.append(torch.sparse_coo_tensor(torch.stack([t(r), t(col.astype(np.int64))]), t(val), (M, K)).coalesce())
+        idx = t(hb.input_nodes.astype(np.int64))
+        x0 = self.feats[idx].float()
+        return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)

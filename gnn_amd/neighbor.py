@@ -199,7 +199,111 @@ class NeighborBatch:
         return iter((self.x0, self.adjs, self.sampled_nodes, self.labels))
 
 
-class NeighborSampler:
+class ResidentSampler:
+    """What the samplers that draw over the resident graph share (``NeighborSampler`` here,
+    ``layerwise.LayerwiseSampler``): the graph and the feature table on the device, the labels and
+    X0 of a batch, the top layer's transpose and row map, and the passes. A subclass provides
+    ``sample(batch_nodes, seed)``."""
+
+    def _setup(self, orders, feats: torch.Tensor, labels_full, device) -> None:
+        who = type(self).__name__
+        self.orders = [int(o) for o in orders]
+        self.N = self.graph.num_nodes
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.native = dev.type == "cuda"
+        if not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.dtype not in cso.FEAT_KIND:
+            raise ValueError(f"{who}: feats must be a 2-D float32 / float16 / bfloat16 tensor")
+        if feats.shape[0] != self.N:
+            raise ValueError(f"{who}: feats has {feats.shape[0]} rows, the graph {self.N} nodes")
+        if labels_full.shape[0] != self.N:
+            raise ValueError(f"{who}: labels_full has {labels_full.shape[0]} rows, the graph {self.N} nodes")
+        self.labels_full = labels_full
+        self.F = int(feats.shape[1])
+        if self.native:
+            self.dgraph = device_graph(self.graph, dev)
+            self.feats = self._resident(feats)
+        else:
+            if feats.is_cuda:
+                raise ValueError(f"{who}: device='cpu' takes a host feature table")
+            self.dgraph = None
+            self.feats = feats
+
+    # ------------------------------------------------------------------ set-up
+    def _free_bytes(self) -> int:
+        free, _ = torch.cuda.mem_get_info(self.device)
+        return int(free) + int(torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device))
+
+    def _resident(self, feats: torch.Tensor) -> torch.Tensor:
+        """The table on the device with unit column stride: itself, or one upload into whole-line rows."""
+        from . import _lib
+        from .staging import padded_ld
+
+        if feats.is_cuda:
+            if feats.device != self.device:
+                raise ValueError(f"{type(self).__name__}: feats is on another device")
+            return feats if feats.stride(1) == 1 else feats.contiguous()
+        esz = feats.element_size()
+        ld = padded_ld(self.F, 128 // esz)
+        need = self.N * ld * esz
+        free = self._free_bytes()
+        if need > free:
+            raise RuntimeError(f"{type(self).__name__}: the feature table needs {need} bytes of device memory, "
+                               f"{free} free: a partially buffered feature store is out of scope")
+        with _lib.on_device(self.device):
+            table = torch.zeros((self.N, ld), dtype=feats.dtype, device=self.device)[:, : self.F]
+            table.copy_(feats)
+        return table
+
+    def _labels(self, q: np.ndarray) -> torch.Tensor:
+        lf = self.labels_full
+        if sp.issparse(lf):
+            lab = np.asarray(lf[q].todense(), dtype=np.float32)
+        elif isinstance(lf, torch.Tensor):
+            lab = lf[torch.from_numpy(q)].to(torch.float32).cpu().numpy()
+        else:
+            lab = np.asarray(lf[q], dtype=np.float32)
+        t = torch.from_numpy(np.ascontiguousarray(lab.reshape(q.size, -1)))
+        return t.to(self.device) if self.native else t
+
+    def _top_maps(self, op, sn: torch.Tensor, M: int, K: int, with_rmap: bool) -> None:
+        """The backward's operand and the fused residual's row map of a layer above layer 0."""
+        op.transpose()
+        if with_rmap:
+            rmap = torch.full((K,), -1, dtype=torch.int32, device=self.device)
+            rmap[sn] = torch.arange(M, dtype=torch.int32, device=self.device)
+            sn._gnn_rmap = rmap
+
+    def _x0(self, idx: torch.Tensor) -> torch.Tensor:
+        """feats[idx] as fp32 whole-line rows (16-bit rows widened exactly): gnn_gather_rows_*."""
+        from .staging import padded_ld
+
+        n = int(idx.numel())
+        x0 = torch.empty((n, padded_ld(self.F, 32)), dtype=torch.float32, device=self.device)[:, : self.F]
+        if n:
+            cso.gather_rows(self.feats, idx, x0, None, n=n)
+        return x0
+
+    # ------------------------------------------------------------------ passes
+    def epoch(self, nodes, batch_size: int, seed: int, shuffle: bool = True) -> Iterator[NeighborBatch]:
+        """Batches of ``batch_size`` over ``nodes`` (shuffled by ``seed`` unless ``shuffle`` is
+        False), the last one short; batch b draws under ``batch_seed(seed, b)``."""
+        from .loader import sequential_chunks
+
+        nodes = np.asarray(nodes)
+        if shuffle:
+            nodes = nodes[np.random.default_rng(int(seed) & 0xFFFFFFFFFFFFFFFF).permutation(len(nodes))]
+        for b, chunk in enumerate(sequential_chunks(nodes, batch_size)):
+            yield self.sample(chunk, batch_seed(seed, b))
+
+    def sequential(self, nodes, batch_size: int, seed: int = 0) -> Iterator[NeighborBatch]:
+        """``nodes`` in order, in chunks of ``batch_size`` (validation / test passes)."""
+        return self.epoch(nodes, batch_size, seed, shuffle=False)
+
+
+class NeighborSampler(ResidentSampler):
     """Neighbour-sampled batches of ``lap`` for a model with layer ``orders`` (0 / 1, bottom-up).
 
     ``fanouts``: one int, or one per aggregating layer (bottom-up, as ``orders``), each in [1, 64].
@@ -222,66 +326,7 @@ class NeighborSampler:
     def __init__(self, lap, fanouts, orders, feats: torch.Tensor, labels_full, device):
         self.graph = _graph_of(lap)
         self.fanouts = _fanout_list(fanouts, orders)
-        self.orders = [int(o) for o in orders]
-        self.N = self.graph.num_nodes
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        self.native = dev.type == "cuda"
-        if not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.dtype not in cso.FEAT_KIND:
-            raise ValueError("NeighborSampler: feats must be a 2-D float32 / float16 / bfloat16 tensor")
-        if feats.shape[0] != self.N:
-            raise ValueError(f"NeighborSampler: feats has {feats.shape[0]} rows, the graph {self.N} nodes")
-        if labels_full.shape[0] != self.N:
-            raise ValueError(f"NeighborSampler: labels_full has {labels_full.shape[0]} rows, the graph {self.N} nodes")
-        self.labels_full = labels_full
-        self.F = int(feats.shape[1])
-        if self.native:
-            self.dgraph = device_graph(self.graph, dev)
-            self.feats = self._resident(feats)
-        else:
-            if feats.is_cuda:
-                raise ValueError("NeighborSampler: device='cpu' takes a host feature table")
-            self.dgraph = None
-            self.feats = feats
-
-    # ------------------------------------------------------------------ set-up
-    def _free_bytes(self) -> int:
-        free, _ = torch.cuda.mem_get_info(self.device)
-        return int(free) + int(torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device))
-
-    def _resident(self, feats: torch.Tensor) -> torch.Tensor:
-        """The table on the device with unit column stride: itself, or one upload into whole-line rows."""
-        from . import _lib
-        from .staging import padded_ld
-
-        if feats.is_cuda:
-            if feats.device != self.device:
-                raise ValueError("NeighborSampler: feats is on another device")
-            return feats if feats.stride(1) == 1 else feats.contiguous()
-        esz = feats.element_size()
-        ld = padded_ld(self.F, 128 // esz)
-        need = self.N * ld * esz
-        free = self._free_bytes()
-        if need > free:
-            raise RuntimeError(f"NeighborSampler: the feature table needs {need} bytes of device memory, {free} free: "
-                               "a partially buffered feature store is out of scope")
-        with _lib.on_device(self.device):
-            table = torch.zeros((self.N, ld), dtype=feats.dtype, device=self.device)[:, : self.F]
-            table.copy_(feats)
-        return table
-
-    def _labels(self, q: np.ndarray) -> torch.Tensor:
-        lf = self.labels_full
-        if sp.issparse(lf):
-            lab = np.asarray(lf[q].todense(), dtype=np.float32)
-        elif isinstance(lf, torch.Tensor):
-            lab = lf[torch.from_numpy(q)].to(torch.float32).cpu().numpy()
-        else:
-            lab = np.asarray(lf[q], dtype=np.float32)
-        t = torch.from_numpy(np.ascontiguousarray(lab.reshape(q.size, -1)))
-        return t.to(self.device) if self.native else t
+        self._setup(orders, feats, labels_full, device)
 
     # ------------------------------------------------------------------ one batch
     def sample(self, batch_nodes, seed: int) -> NeighborBatch:
@@ -342,27 +387,13 @@ class NeighborSampler:
                                               err.data_ptr(), st), "gnn_nbr_relabel")
                 sn = cso.closure_rank(table, N, rows)
                 op = cso.CsrOperand(rowptr, col, val, (M, K))
-                if l >= 1:  # the backward's operand and the fused residual's row map
-                    op.transpose()
-                    if unique_top or not top:
-                        rmap = torch.full((K,), -1, dtype=torch.int32, device=dev)
-                        rmap[sn] = torch.arange(M, dtype=torch.int32, device=dev)
-                        sn._gnn_rmap = rmap
+                if l >= 1:
+                    self._top_maps(op, sn, M, K, unique_top or not top)
                 adjs[l], sampled[l] = op, sn
                 rows, top = low, False
             input_nodes = rows.long()
             x0 = self._x0(input_nodes)
         return NeighborBatch(x0, adjs, sampled, self._labels(q), input_nodes, q, seed)
-
-    def _x0(self, idx: torch.Tensor) -> torch.Tensor:
-        """feats[idx] as fp32 whole-line rows (16-bit rows widened exactly): gnn_gather_rows_*."""
-        from .staging import padded_ld
-
-        n = int(idx.numel())
-        x0 = torch.empty((n, padded_ld(self.F, 32)), dtype=torch.float32, device=self.device)[:, : self.F]
-        if n:
-            cso.gather_rows(self.feats, idx, x0, None, n=n)
-        return x0
 
     def _sample_cpu(self, q: np.ndarray, seed: int) -> NeighborBatch:
         hb = neighbor_sample_host(seed, q, [f for f in self.fanouts if f is not None], self.graph, self.orders)
@@ -379,19 +410,3 @@ class NeighborSampler:
         idx = t(hb.input_nodes.astype(np.int64))
         x0 = self.feats[idx].float()
         return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)
-
-    # ------------------------------------------------------------------ passes
-    def epoch(self, nodes, batch_size: int, seed: int, shuffle: bool = True) -> Iterator[NeighborBatch]:
-        """Batches of ``batch_size`` over ``nodes`` (shuffled by ``seed`` unless ``shuffle`` is
-        False), the last one short; batch b draws under ``batch_seed(seed, b)``."""
-        from .loader import sequential_chunks
-
-        nodes = np.asarray(nodes)
-        if shuffle:
-            nodes = nodes[np.random.default_rng(int(seed) & 0xFFFFFFFFFFFFFFFF).permutation(len(nodes))]
-        for b, chunk in enumerate(sequential_chunks(nodes, batch_size)):
-            yield self.sample(chunk, batch_seed(seed, b))
-
-    def sequential(self, nodes, batch_size: int, seed: int = 0) -> Iterator[NeighborBatch]:
-        """``nodes`` in order, in chunks of ``batch_size`` (validation / test passes)."""
-        return self.epoch(nodes, batch_size, seed, shuffle=False)

@@ -175,6 +175,86 @@ int gnn_nbr_draw(const int64_t* indptr, const int32_t* indices, int64_t num_node
 int gnn_nbr_relabel(const void* table, int64_t num_nodes, const int32_t* ids, int64_t n, int32_t* col, float* val,
                     int32_t* err_flag, void* stream);
 
+/* The LADIES layer draw on the device: a hashed race over the resident graph (layerwise.hip).
+ *
+ * The reference (sampler.py:113-139) takes U = lap[rows, :] (rows: the layer's output nodes, in
+ * order, repeats kept), pi = U's entry count per column, p = pi / sum(pi), s_num = min(number of
+ * live columns, samp_num), and draws np.random.choice(N, s_num, p = p, replace = False):
+ * successive sampling without replacement, proportional to integer weights. The same law comes from
+ * a race: give every entry of U an independent uniform value and every column the maximum over its
+ * entries; the overall maximum is equally likely to be any entry, so column j leads with
+ * probability pi_j / sum(pi), and removing that column leaves the same situation among the rest.
+ * The s_num columns with the largest maxima are distributed exactly as np.random.choice's set.
+ *
+ * The draw, in 64-bit unsigned arithmetic mod 2^64 (a pure integer function of the seed):
+ *   mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *             z ^= z >> 31                                   (the splitmix64 finaliser)
+ *   K = mix64(seed + (layer + 1) * 0x9E3779B97F4A7C15), layer = the model's layer index (0 = bottom)
+ *   the entry of U in row position i (its index in rows, not the node id: a repeated row counts
+ *   again, as the reference's U does) and column node id c:  h(i, c) = mix64((c << 32 | i) + K)
+ *   key[c] = max_i h(i, c), count[c] = the number of entries; a column is live iff count[c] > 0.
+ *   mix64 is a bijection and (c, i) is unique per entry, so all entry values, hence all column
+ *   keys, are distinct: no tie rule exists or is needed.
+ *   s_num = min(nlive, samp_num); selected = the s_num live columns with the largest keys;
+ *   after = unique(selected ++ rows);
+ *   normfact[k] = 1.0f / (float)clip((double)s_num * ((double)count[after[k]] / (double)sum(count)),
+ *                                    1e-10, 1.0)
+ *   (sampler.py:137: the clipped value is cast to float32 before the reciprocal, a float32 division;
+ *   the ratio counts as 0 when nothing was counted). A row node that is nobody's column has count 0,
+ *   hence normfact 1 / float32(1e-10) and an empty column. adj = lap[rows, :][:, after] with
+ *   gnn_ladies_extract_f32's values.
+ *
+ * A layer on the device, everything on one stream up to one read of (K, totals, flag):
+ *   gnn_closure_mark(seeds = rows, expand = 1) -> the live table: the columns of U and (the mark sets
+ *     its seeds too) the rows themselves, ntab members;  gnn_closure_list -> tab_ids
+ *   gnn_lw_race -> count, key, sum(count);  gnn_lw_select -> s_num, tau, ids
+ *   gnn_closure_mark(seeds = rows ++ ids, expand = 0) -> the table of after, K;  gnn_closure_list -> after
+ *   gnn_lw_finish -> normfact and gnn_ladies_extract_f32's offsets and totals.
+ *
+ * race: count int32[cap] / key uint64[cap], indexed by the column's position in the live table (its
+ *   rank lookup: no array over num_nodes), are zero-filled and then filled; *total (device int64) =
+ *   sum(count). cap >= ntab; min(num_nodes, M + sum of deg(rows)) suffices. A member that is only a
+ *   row keeps count 0 and key 0. A wave per row, the row's entries over the lanes; one 32-bit add
+ *   and one 64-bit max per entry.
+ * select: over the positions j < *ntab (device int64, clamped to cap) with count[j] > 0, the nlive
+ *   live columns: *s_num (device int64) = min(nlive, samp_num), *tau (device uint64) = the s_num-th
+ *   largest of their keys (0 when s_num = 0), ids[j] = (count[j] > 0 and key[j] >= tau) ?
+ *   tab_ids[j] : -1 for j < ntab and -1 for ntab <= j < cap (gnn_closure_mark skips -1: no
+ *   compaction). An exact radix select on the full 64 bits, eight passes of LDS histograms, its
+ *   state kept in the workspace (gnn_lw_select_workspace_bytes()); exactly s_num entries pass,
+ *   because keys are distinct. Nothing at or past ntab is read.
+ * finish: for after int32[*K] (*K device int64, clamped to kcap; the list of the second table):
+ *   normfact fp32[K] (count looked up through the live table, 0 for a non-member),
+ *   colptr_t int32[K+1] = the exclusive scan of count[after] (closing entry: the operand's nnz),
+ *   rowseg int32[M+1] = the scan of deg(rows), colseg int32[K+1] = the scan of lap^T's row lengths
+ *   of after, totals int64[3] (device) = nnz, colseg[K], sum of deg(after) (the next layer's
+ *   rowseg[M]). A sum of 2^31 or more ORs 1 into err_flag; its offsets are then all zero and its
+ *   total reads 2^31 - 1, so the outputs stay safe to read. workspace:
+ *   gnn_lw_finish_workspace_bytes(M, kcap).
+ *
+ * Memory safety does not depend on the contents of the device arrays: a row id outside
+ * [0, num_nodes), a row pointer outside [0, num_entries] or running backwards, a column that is not
+ * in the live table or sits at a position >= cap contribute nothing; *ntab and *K are clamped to
+ * cap and kcap. Each case ORs 1 into err_flag (device int32, optional).
+ *
+ * Conventions as above: device pointers, stream-ordered, no allocation, no host synchronisation.
+ * Refused with GNN_EINVAL before anything is launched: a negative size, a size >= 2^31,
+ * samp_num < 1, a negative layer, a NULL pointer where one is read or written, a misaligned table
+ * or 8-byte word, a workspace that is NULL, too small or not 16-byte aligned. */
+int gnn_lw_race(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
+                const int32_t* rows, int64_t M, const void* live_table, uint64_t seed, int32_t layer, int32_t* count,
+                uint64_t* key, int64_t cap, int64_t* total, int32_t* err_flag, void* stream);
+size_t gnn_lw_select_workspace_bytes(void);
+int gnn_lw_select(const uint64_t* key, const int32_t* count, const int64_t* ntab, int64_t cap, int64_t samp_num,
+                  const int32_t* tab_ids, int32_t* ids, int64_t* s_num, uint64_t* tau, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t gnn_lw_finish_workspace_bytes(int64_t M, int64_t kcap);
+int gnn_lw_finish(const int64_t* indptr, int64_t num_entries, const int64_t* indptr_t, int64_t num_entries_t,
+                  int64_t num_nodes, const int32_t* rows, int64_t M, const int32_t* after, const int64_t* K,
+                  int64_t kcap, const void* live_table, const int32_t* count, int64_t cap, const int64_t* total,
+                  const int64_t* s_num, float* normfact, int32_t* colptr_t, int32_t* rowseg, int32_t* colseg,
+                  int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
