@@ -78,6 +78,7 @@ _SIGNATURES = {
     "gnn_gather_rows2_h16_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _INT, _VP, _I64, _I64,
                                         _VP]),
     "gnn_gather_rows_host_f32": (_INT, [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP]),
+    "gnn_gather_placed_f32": (_INT, [_VP, _I64, _VP, _INT, _VP, _I64, _INT, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _VP]),
     "gnn_host_register": (_INT, [_VP, _SZ]),
     "gnn_host_unregister": (_INT, [_VP]),
     "gnn_memcpy_h2d_async": (_INT, [_VP, _VP, _SZ, _VP]),

@@ -198,8 +198,8 @@ class LayerwiseSampler(ResidentSampler):
     the next layer's read, and of one last read per batch. With ``device="cpu"`` the same batches
     come from ``ladies_race_host`` as torch COO operands.
 
-    Out of scope, refused: weighted graphs, scale_factor > 1, FastGCN, subgraph sampling, rank
-    splitting; ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
+    Out of scope, refused: weighted graphs, scale_factor > 1, FastGCN, subgraph sampling;
+    ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
 
     def __init__(self, lap, samp_num, orders, feats: torch.Tensor, labels_full, device, scale_factor: float = 1.0):
         if scale_factor > 1:
@@ -332,5 +332,5 @@ class LayerwiseSampler(ResidentSampler):
             # create_coo_tensor's CPU branch: the same values, coalesced
             adjs.append(torch.sparse_coo_tensor(torch.stack([t(r), t(col.astype(np.int64))]), t(val), (M, K)).coalesce())
         idx = t(hb.input_nodes.astype(np.int64))
-        x0 = self.feats[idx].float()
+        x0 = self._x0_host(idx)
         return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)

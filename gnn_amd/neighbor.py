@@ -205,7 +205,9 @@ class ResidentSampler:
     X0 of a batch, the top layer's transpose and row map, and the passes. A subclass provides
     ``sample(batch_nodes, seed)``."""
 
-    def _setup(self, orders, feats: torch.Tensor, labels_full, device) -> None:
+    def _setup(self, orders, feats, labels_full, device) -> None:
+        from .placed import PlacedFeatures
+
         who = type(self).__name__
         self.orders = [int(o) for o in orders]
         self.N = self.graph.num_nodes
@@ -214,8 +216,12 @@ class ResidentSampler:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.native = dev.type == "cuda"
-        if not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.dtype not in cso.FEAT_KIND:
-            raise ValueError(f"{who}: feats must be a 2-D float32 / float16 / bfloat16 tensor")
+        self.placed = isinstance(feats, PlacedFeatures)
+        if self.placed:
+            if feats.device != dev:
+                raise ValueError(f"{who}: feats (a PlacedFeatures) is on {feats.device}, the sampler on {dev}")
+        elif not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.dtype not in cso.FEAT_KIND:
+            raise ValueError(f"{who}: feats must be a 2-D float32 / float16 / bfloat16 tensor or a PlacedFeatures")
         if feats.shape[0] != self.N:
             raise ValueError(f"{who}: feats has {feats.shape[0]} rows, the graph {self.N} nodes")
         if labels_full.shape[0] != self.N:
@@ -224,9 +230,9 @@ class ResidentSampler:
         self.F = int(feats.shape[1])
         if self.native:
             self.dgraph = device_graph(self.graph, dev)
-            self.feats = self._resident(feats)
+            self.feats = feats if self.placed else self._resident(feats)
         else:
-            if feats.is_cuda:
+            if not self.placed and feats.is_cuda:
                 raise ValueError(f"{who}: device='cpu' takes a host feature table")
             self.dgraph = None
             self.feats = feats
@@ -251,7 +257,8 @@ class ResidentSampler:
         free = self._free_bytes()
         if need > free:
             raise RuntimeError(f"{type(self).__name__}: the feature table needs {need} bytes of device memory, "
-                               f"{free} free: a partially buffered feature store is out of scope")
+                               f"{free} free: a partially buffered feature store is out of scope here "
+                               "(placed.PlacedFeatures serves one)")
         with _lib.on_device(self.device):
             table = torch.zeros((self.N, ld), dtype=feats.dtype, device=self.device)[:, : self.F]
             table.copy_(feats)
@@ -277,26 +284,46 @@ class ResidentSampler:
             sn._gnn_rmap = rmap
 
     def _x0(self, idx: torch.Tensor) -> torch.Tensor:
-        """feats[idx] as fp32 whole-line rows (16-bit rows widened exactly): gnn_gather_rows_*."""
+        """feats[idx] as fp32 whole-line rows (16-bit rows widened exactly): gnn_gather_rows_*, or
+        over a placed store gnn_gather_placed_f32."""
         from .staging import padded_ld
 
+        if self.placed:
+            return self.feats.gather(idx)
         n = int(idx.numel())
         x0 = torch.empty((n, padded_ld(self.F, 32)), dtype=torch.float32, device=self.device)[:, : self.F]
         if n:
             cso.gather_rows(self.feats, idx, x0, None, n=n)
         return x0
 
+    def _x0_host(self, idx: torch.Tensor) -> torch.Tensor:
+        """The ``device="cpu"`` form of ``_x0``."""
+        return self.feats.gather(idx) if self.placed else self.feats[idx].float()
+
     # ------------------------------------------------------------------ passes
-    def epoch(self, nodes, batch_size: int, seed: int, shuffle: bool = True) -> Iterator[NeighborBatch]:
+    def epoch(self, nodes, batch_size: int, seed: int, shuffle: bool = True, rank: int = 0,
+              world_size: int = 1) -> Iterator[NeighborBatch]:
         """Batches of ``batch_size`` over ``nodes`` (shuffled by ``seed`` unless ``shuffle`` is
-        False), the last one short; batch b draws under ``batch_seed(seed, b)``."""
+        False), the last one short; batch b draws under ``batch_seed(seed, b)``. With ``world_size``
+        ranks the list — the same on every rank, the seed being the same — is cut into the
+        reference's contiguous chunks of ceil(n / world_size) (sampler.py:170-175, as
+        ``sampler.rank_batches``) and ``rank`` takes its own. A pass over a placed store ends with
+        its ``check()``."""
         from .loader import sequential_chunks
 
         nodes = np.asarray(nodes)
+        if not 0 <= rank < world_size:
+            raise ValueError(f"{type(self).__name__}.epoch: rank {rank} outside a world of {world_size}")
         if shuffle:
             nodes = nodes[np.random.default_rng(int(seed) & 0xFFFFFFFFFFFFFFFF).permutation(len(nodes))]
+        if world_size > 1:
+            n = len(nodes)
+            chunk_size = n // world_size + (1 if n % world_size else 0)
+            nodes = nodes[rank * chunk_size: min((rank + 1) * chunk_size, n)]
         for b, chunk in enumerate(sequential_chunks(nodes, batch_size)):
             yield self.sample(chunk, batch_seed(seed, b))
+        if self.placed:
+            self.feats.check()
 
     def sequential(self, nodes, batch_size: int, seed: int = 0) -> Iterator[NeighborBatch]:
         """``nodes`` in order, in chunks of ``batch_size`` (validation / test passes)."""
@@ -308,7 +335,9 @@ class NeighborSampler(ResidentSampler):
 
     ``fanouts``: one int, or one per aggregating layer (bottom-up, as ``orders``), each in [1, 64].
     ``feats``: the float32 / float16 / bfloat16 feature table [N, F]; on a GPU it lives on the
-    device (a host table is uploaded once; one that does not fit is refused with the byte count).
+    device (a host table is uploaded once; one that does not fit is refused with the byte count),
+    or a ``placed.PlacedFeatures`` on the sampler's device: the table served from the placement's
+    sources — this rank's buffer, the peers' buffers, the host table — by node id.
     ``labels_full``: dense or scipy-sparse [N, C]; a batch's rows are gathered on the host (the
     batch nodes are host data) and uploaded.
 
@@ -408,5 +437,5 @@ class NeighborSampler(ResidentSampler):
             # normfact = 1: value = (float)((1.0 / k) * 1.0), the device draw's weight
             adjs.append(cso.create_coo_tensor(t(rowptr), t(rowptr), t(col), torch.ones(K), M, K))
         idx = t(hb.input_nodes.astype(np.int64))
-        x0 = self.feats[idx].float()
+        x0 = self._x0_host(idx)
         return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)

@@ -300,6 +300,52 @@ int gnn_gather_rows_host_f32(const float* host_src, int64_t ld_src, const int64_
                              float* dst, int64_t ld_dst, const int64_t* dst_idx,
                              int64_t n, int64_t F, void* stream);
 
+/* X0 by node id over a placed feature store: dst[i, 0:F] = (float) row(nodes[i])[0:F], where the
+ * row's source is looked up on the device, in this rank's placement map — the device draws'
+ * (gnn_extract.h: gnn_nbr_*, gnn_lw_*) input nodes exist only there, so no host mask, slot list
+ * or compaction can be made for them (main.py:129-134 assembles X0 from the same three sources by
+ * host masks).
+ *
+ * place int32[num_nodes] (device): GNN_PLACE_HOST (-1) = the row is row `node` of the host table;
+ * otherwise src << GNN_PLACE_SHIFT | slot: row `slot` of source `src` — the reference's
+ * device_id_of_nodes and idx_of_nodes_on_device (preprocess.py:343-386) in one word. srcs (device,
+ * nsrc <= GNN_PLACE_MAX_SRC entries, uploaded once): per source its base, row stride `ld` in its
+ * elements and row count; source 0 is the rank's own buffer, the others mapped peer buffers
+ * (gnn_ipc_open). `kind` (GNN_FEAT_*) names the elements of every source and of the host table;
+ * 16-bit rows are widened exactly. host_table is host memory registered with gnn_host_register
+ * (NULL: none), any stride ld_host >= F and any element-aligned base; nodes int32[n] (device).
+ *
+ * One launch: the first workgroups (at most 32) walk the positions for host-placed nodes — a
+ * contiguous range per wave, 64 map values at a time, the host ones balloted and read over PCIe two
+ * rows at a time — while the others take one device row per wave; the load width is chosen per
+ * source from its base and stride, within what dst allows, so a narrow host table does not
+ * narrow the buffer rows; a row's columns past its last whole vector move one per lane, so F need
+ * not be a multiple of the width (602-column rows move by 16-byte loads). counts (device int64[nsrc + 1], may be NULL) is ADDED to: the rows each
+ * source served, the host last (one relaxed add per walker wave; integer adds, so deterministic).
+ *
+ * A row that cannot be served is stored as zeros and ORs 1 into *flag (device int32): a node
+ * outside [0, num_nodes), a source index >= nsrc, a slot >= its source's rows, a source with a NULL
+ * base or ld < F, a host-placed node with a NULL host_table. Nothing outside a source is read.
+ * Stream-ordered, no allocation, no host read, graph-capturable. Refused with GNN_EINVAL before
+ * anything is launched: an unknown kind, nsrc outside [1, 16], a negative size, num_nodes, n or F
+ * >= 2^31, F > ld_dst, F > ld_host (with a host table) and, for n > 0 and F > 0, a NULL place, srcs,
+ * nodes, dst or flag or a misaligned host_table / dst. */
+#define GNN_PLACE_HOST (-1)
+#define GNN_PLACE_SHIFT 27
+#define GNN_PLACE_MAX_SRC 16
+typedef struct gnn_place_src {
+  const void* base;
+  int64_t ld;
+  int64_t rows;
+} gnn_place_src;
+int gnn_gather_placed_f32(const int32_t* place, int64_t num_nodes,
+                          const gnn_place_src* srcs, int nsrc,
+                          const void* host_table, int64_t ld_host,
+                          int kind,
+                          const int32_t* nodes, int64_t n,
+                          float* dst, int64_t ld_dst, int64_t F,
+                          int64_t* counts, int32_t* flag, void* stream);
+
 /* Pin + map a host range for device access (hipHostRegister, mapped) / undo it. */
 int gnn_host_register(void* host, size_t bytes);
 int gnn_host_unregister(void* host);
