@@ -63,6 +63,11 @@ _SIGNATURES = {
     "gnn_lw_finish_workspace_bytes": (_SZ, [_I64, _I64]),
     "gnn_lw_finish": (_INT, [_VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP,
                              _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
+    # the plain entry points' arguments, then (favoured, scale)
+    "gnn_lw_race_skew": (_INT, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, ctypes.c_uint64, ctypes.c_int32, _VP, _VP, _I64,
+                                _VP, _VP, _VP, _VP, ctypes.c_int32]),
+    "gnn_lw_finish_skew": (_INT, [_VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP, _VP, ctypes.c_int32]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

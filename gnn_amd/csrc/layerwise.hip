@@ -28,6 +28,10 @@
 //   gnn_lw_finish  lw_chunk_scan (blockIdx.y = which scan; closure.hip's cl_chunk_scan shape; also
 //                  normfact and the exact 64-bit totals), scan_exclusive over the chunk sums of each
 //                  scan, lw_chunk_add (offsets, the closing entries, the totals and their clamp).
+// The locality-skewed draw (gnn_lw_race_skew / gnn_lw_finish_skew: a favoured bit table and an integer
+// scale) gives an entry of a favoured column `scale` replicas; the race takes their maximum in
+// registers after one 4-byte read of the column's favoured word, and finish weighs normfact by
+// count * s(c). The plain entry points are the skewed ones with (NULL, 1): the unskewed instantiation.
 // Memory safety does not depend on the contents of the device arrays: a row id outside the graph,
 // a row pointer outside [0, num_entries] or running backwards, a column outside the live table or
 // at a position >= cap contribute nothing; device-side sizes (the table's, K) are clamped to the host's
@@ -68,10 +72,21 @@ __host__ __device__ __forceinline__ u64 mix64(u64 z) {  // the splitmix64 finali
   return z ^ (z >> 31);
 }
 
+// s(c) of the skewed draw: `scale` for a node of the favoured bit table (bit c & 31 of word c >> 5),
+// else 1. c has passed table_pos, so 0 <= c < N and the word lies inside the table.
+__device__ __forceinline__ int lw_replicas(const uint32_t* __restrict__ favoured, int scale, int c) {
+  return ((favoured[c >> 5] >> ((unsigned)c & 31u)) & 1u) ? scale : 1;
+}
+
+// SKEW: an entry of a favoured column races with `scale` replicas, replica r under the value
+// mix64((c << 32 | r << 26 | i) + K) (M < 2^26, the host has checked); their maximum is taken in
+// registers, so an entry still costs one add and one max. The wave adds s(c) per entry to total.
+template <bool SKEW>
 __global__ __launch_bounds__(64 * LW_RACE_WAVES) void lw_race_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int N, int64_t E,
     const int32_t* __restrict__ rows, int M, const Word* __restrict__ live, u64 K, int32_t* __restrict__ count,
-    u64* __restrict__ key, int cap, i64* __restrict__ total, int32_t* __restrict__ err) {
+    u64* __restrict__ key, int cap, i64* __restrict__ total, int32_t* __restrict__ err,
+    const uint32_t* __restrict__ favoured, int scale) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * LW_RACE_WAVES + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * LW_RACE_WAVES;
@@ -88,10 +103,19 @@ __global__ __launch_bounds__(64 * LW_RACE_WAVES) void lw_race_kernel(
         bad = true;
         continue;
       }
+      u64 h = mix64((((u64)(uint32_t)c << 32) | (u64)(uint32_t)i) + K);
+      if constexpr (SKEW) {
+        const int s = lw_replicas(favoured, scale, c);
+        for (int r = 1; r < s; ++r) {
+          const u64 hr = mix64((((u64)(uint32_t)c << 32) | ((u64)r << 26) | (u64)(uint32_t)i) + K);
+          h = hr > h ? hr : h;
+        }
+        mine += s;
+      } else {
+        ++mine;
+      }
       (void)__hip_atomic_fetch_add(&count[p], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      (void)__hip_atomic_fetch_max(&key[p], mix64((((u64)(uint32_t)c << 32) | (u64)(uint32_t)i) + K),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ++mine;
+      (void)__hip_atomic_fetch_max(&key[p], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 #pragma unroll
@@ -195,10 +219,11 @@ __global__ __launch_bounds__(LW_BINS) void lw_select_write_kernel(const u64* __r
     ids[j] = (sn > 0 && j < n && count[j] > 0 && key[j] >= t) ? tab_ids[j] : -1;
 }
 
-// normfact of a column counted cnt times among total entries, s_num columns drawn: the reference's
-// 1 / float32(clip(s_num * p, 1e-10, 1)) with p = cnt / total in fp64 (0 when nothing was counted)
-__device__ __forceinline__ float lw_normfact(int cnt, i64 total, i64 s_num) {
-  double q = total > 0 ? (double)s_num * ((double)cnt / (double)total) : 0.0;
+// normfact of a column of weight w (its entry count, times s(c) in the skewed draw) among a total
+// weight of total, s_num columns drawn: the reference's 1 / float32(clip(s_num * p, 1e-10, 1)) with
+// p = w / total in fp64 (0 when nothing was counted)
+__device__ __forceinline__ float lw_normfact(i64 w, i64 total, i64 s_num) {
+  double q = total > 0 ? (double)s_num * ((double)w / (double)total) : 0.0;
   q = q < 1e-10 ? 1e-10 : (q > 1.0 ? 1.0 : q);
   return 1.0f / (float)q;
 }
@@ -226,6 +251,8 @@ struct FinishArgs {
   i64* tot;                // [4]: the sums of the three scans and of deg(after), exact
   int64_t* totals;         // the caller's (nnz, colseg total, deg(after) total)
   int32_t* err;
+  const uint32_t* favoured;  // the skewed draw's bit table, or NULL: every weight is the count
+  int scale;
 };
 
 // blockIdx.y = which: 0 count[after[k]] (and normfact), 1 deg(rows[i]), 2 lap^T's row length of
@@ -250,7 +277,9 @@ __global__ __launch_bounds__(1024) void lw_chunk_scan_kernel(FinishArgs a) {
         const int p = table_pos(a.live, a.N, a.after[base + k]);
         d = (p >= 0 && p < a.cap) ? a.count[p] : 0;
         if (d < 0) d = 0;
-        a.normfact[base + k] = lw_normfact(d, *a.total, *a.s_num);
+        i64 w = d;  // p >= 0: after[base + k] lies in [0, N), inside the favoured table
+        if (a.favoured && d > 0) w *= lw_replicas(a.favoured, a.scale, a.after[base + k]);
+        a.normfact[base + k] = lw_normfact(w, *a.total, *a.s_num);
       } else if (which == 1) {
         bad |= !row_span(a.indptr, a.N, a.E, a.rows[base + k], b, d);
       } else if (which == 2) {
@@ -329,6 +358,16 @@ inline size_t csum_bytes(int64_t n) {
   return align_up(((size_t)ceil_div(n, (int64_t)LW_CHUNK) + 1) * sizeof(int32_t), 256);
 }
 
+// What the two skewed entry points refuse of (favoured, scale): replica r sits in bits 26 .. 31 of
+// the hashed word and the row position below it, hence scale <= 64 and M < 2^26 where replicas race.
+inline int skew_ok(const char* fn, const uint32_t* favoured, int32_t scale, int64_t M) {
+  GNN_REQUIRE(scale >= 1 && scale <= 64, "%s: scale %d outside [1, 64]", fn, (int)scale);
+  GNN_REQUIRE((uintptr_t)favoured % 4 == 0, "%s: favoured table not 4-byte aligned", fn);
+  GNN_REQUIRE(!(favoured && scale > 1) || M < ((int64_t)1 << 26),
+              "%s: a skewed race needs M < 2^26 rows (the row position shares a word with the replica)", fn);
+  return 0;
+}
+
 constexpr size_t SEL_HIST_BYTES = (size_t)LW_PASSES * LW_BINS * sizeof(unsigned);
 constexpr size_t SEL_STATE_BYTES = (size_t)(LW_PASSES + 1) * sizeof(SelState);
 
@@ -339,6 +378,14 @@ extern "C" {
 int gnn_lw_race(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
                 const int32_t* rows, int64_t M, const void* live_table, uint64_t seed, int32_t layer, int32_t* count,
                 uint64_t* key, int64_t cap, int64_t* total, int32_t* err_flag, void* stream) {
+  return gnn_lw_race_skew(indptr, indices, num_nodes, num_entries, rows, M, live_table, seed, layer, count, key, cap,
+                          total, err_flag, stream, nullptr, 1);
+}
+
+int gnn_lw_race_skew(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
+                     const int32_t* rows, int64_t M, const void* live_table, uint64_t seed, int32_t layer,
+                     int32_t* count, uint64_t* key, int64_t cap, int64_t* total, int32_t* err_flag, void* stream,
+                     const uint32_t* favoured, int32_t scale) {
   GNN_REQUIRE(num_nodes >= 0 && num_entries >= 0 && M >= 0 && cap >= 0,
               "gnn_lw_race: negative size (num_nodes, num_entries, M or cap)");
   GNN_REQUIRE(num_nodes < INT_MAX && M < INT_MAX && cap < INT_MAX, "gnn_lw_race: num_nodes, M and cap must be < 2^31");
@@ -350,6 +397,9 @@ int gnn_lw_race(const int64_t* indptr, const int32_t* indices, int64_t num_nodes
   GNN_REQUIRE((uintptr_t)key % 8 == 0 && (uintptr_t)total % 8 == 0, "gnn_lw_race: key/total not 8-byte aligned");
   GNN_REQUIRE(M == 0 || (indptr && rows), "gnn_lw_race: NULL indptr/rows");
   GNN_REQUIRE(M == 0 || num_entries == 0 || indices, "gnn_lw_race: NULL indices");
+  int rc = skew_ok("gnn_lw_race_skew", favoured, scale, M);
+  if (rc) return rc;
+  const bool skew = favoured != nullptr && scale > 1;
   hipStream_t st = (hipStream_t)stream;
   GNN_HIP(hipMemsetAsync(total, 0, sizeof(int64_t), st), "hipMemsetAsync");
   if (cap > 0) {
@@ -359,9 +409,15 @@ int gnn_lw_race(const int64_t* indptr, const int32_t* indices, int64_t num_nodes
   if (M == 0) return 0;
   const u64 K = mix64((u64)seed + ((u64)layer + 1ull) * 0x9E3779B97F4A7C15ull);
   const int64_t g = ceil_div(M, (int64_t)LW_RACE_WAVES);
-  lw_race_kernel<<<dim3((unsigned)(g < LW_RACE_GRID ? g : LW_RACE_GRID)), dim3(64 * LW_RACE_WAVES), 0, st>>>(
-      indptr, indices, (int)num_nodes, num_entries, rows, (int)M, (const Word*)live_table, K, count, (u64*)key, (int)cap,
-      (i64*)total, err_flag);
+  const dim3 grid((unsigned)(g < LW_RACE_GRID ? g : LW_RACE_GRID)), block(64 * LW_RACE_WAVES);
+  if (skew)
+    lw_race_kernel<true><<<grid, block, 0, st>>>(indptr, indices, (int)num_nodes, num_entries, rows, (int)M,
+                                                 (const Word*)live_table, K, count, (u64*)key, (int)cap, (i64*)total,
+                                                 err_flag, favoured, scale);
+  else
+    lw_race_kernel<false><<<grid, block, 0, st>>>(indptr, indices, (int)num_nodes, num_entries, rows, (int)M,
+                                                  (const Word*)live_table, K, count, (u64*)key, (int)cap, (i64*)total,
+                                                  err_flag, nullptr, 1);
   GNN_LAUNCHED("lw_race_kernel");
   return 0;
 }
@@ -409,6 +465,17 @@ int gnn_lw_finish(const int64_t* indptr, int64_t num_entries, const int64_t* ind
                   int64_t kcap, const void* live_table, const int32_t* count, int64_t cap, const int64_t* total,
                   const int64_t* s_num, float* normfact, int32_t* colptr_t, int32_t* rowseg, int32_t* colseg,
                   int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  return gnn_lw_finish_skew(indptr, num_entries, indptr_t, num_entries_t, num_nodes, rows, M, after, K, kcap, live_table,
+                            count, cap, total, s_num, normfact, colptr_t, rowseg, colseg, totals, workspace,
+                            workspace_bytes, err_flag, stream, nullptr, 1);
+}
+
+int gnn_lw_finish_skew(const int64_t* indptr, int64_t num_entries, const int64_t* indptr_t, int64_t num_entries_t,
+                       int64_t num_nodes, const int32_t* rows, int64_t M, const int32_t* after, const int64_t* K,
+                       int64_t kcap, const void* live_table, const int32_t* count, int64_t cap, const int64_t* total,
+                       const int64_t* s_num, float* normfact, int32_t* colptr_t, int32_t* rowseg, int32_t* colseg,
+                       int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream,
+                       const uint32_t* favoured, int32_t scale) {
   GNN_REQUIRE(num_nodes >= 0 && num_entries >= 0 && num_entries_t >= 0 && M >= 0 && kcap >= 0 && cap >= 0,
               "gnn_lw_finish: negative size (num_nodes, num_entries, num_entries_t, M, kcap or cap)");
   GNN_REQUIRE(num_nodes < INT_MAX && M < INT_MAX && kcap < INT_MAX && cap < INT_MAX,
@@ -424,6 +491,8 @@ int gnn_lw_finish(const int64_t* indptr, int64_t num_entries, const int64_t* ind
   GNN_REQUIRE(kcap == 0 || (after && normfact), "gnn_lw_finish: NULL after/normfact");
   GNN_REQUIRE(M == 0 || rows, "gnn_lw_finish: NULL rows");
   GNN_REQUIRE((M == 0 && kcap == 0) || (indptr && indptr_t), "gnn_lw_finish: NULL indptr/indptr_t");
+  int src = skew_ok("gnn_lw_finish_skew", favoured, scale, M);
+  if (src) return src;
   const size_t need = gnn_lw_finish_workspace_bytes(M, kcap);
   GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_lw_finish: workspace too small (%zu < %zu)",
               workspace ? workspace_bytes : (size_t)0, need);
@@ -459,6 +528,8 @@ int gnn_lw_finish(const int64_t* indptr, int64_t num_entries, const int64_t* ind
   a.tot = (i64*)((char*)workspace + 2 * LW_SCANS * cb);
   a.totals = totals;
   a.err = err_flag;
+  a.favoured = scale > 1 ? favoured : nullptr;
+  a.scale = scale;
   GNN_HIP(hipMemsetAsync(a.tot, 0, 4 * sizeof(i64), st), "hipMemsetAsync");
   if (nch > 0) {
     lw_chunk_scan_kernel<<<dim3((unsigned)nch, LW_SCANS + 1), dim3(1024), 0, st>>>(a);

@@ -18,6 +18,15 @@ mix64 is a bijection, so all keys are distinct and no tie rule exists. ``race_ke
 numpy, ``ladies_race_host`` builds the whole batch there (the GPU tests' oracle and the source of
 ``device="cpu"``), ``LayerwiseSampler.sample`` builds the same batch on the GPU, array for array.
 ``layer`` is the model's layer index (0 = the bottom layer, as ``adjs``).
+
+The locality-skewed draw (the reference's sampler.py:119-121 with ``get_skewed_sampled_nodes``: pi of a
+favoured column times ``scale_factor`` before the draw, normfact from the skewed p) keeps all of
+that. With an integer scale in [1, 64] an entry of a favoured column races with ``scale`` replicas,
+  h_r(i, c) = mix64((c << 32 | r << 26 | i) + K), 0 <= r < scale, i < 2^26, h_0 = h,
+so key[c] is the maximum of w[c] = count[c] * s(c) distinct uniform values (s(c) = scale for a favoured
+column, else 1): successive sampling proportional to w, ``np.random.choice``'s law on the scaled
+pi. ``count`` stays the raw entry count, normfact's p becomes w / sum(w). With nothing favoured, or
+scale 1, every array is the plain draw's bit for bit.
 """
 from __future__ import annotations
 
@@ -70,6 +79,71 @@ def entry_values(seed: int, layer: int, i, c) -> np.ndarray:
         return mix64(((c << np.uint64(32)) | (i & np.uint64(0xFFFFFFFF))) + race_key(seed, layer))
 
 
+MAX_SCALE = 64     # replica r sits in 6 bits of the hashed word ...
+REPLICA_SHIFT = 26  # ... above the row position, which therefore stays below 2^26
+
+
+def favoured_bits(ids, N: int) -> np.ndarray:
+    """The favoured set as the device's bit table, uint32[ceil(N / 32)]: node c is bit c & 31 of word c >> 5."""
+    ids = _favoured_ids(ids, N)
+    bits = np.zeros((int(N) + 31) // 32, dtype=np.uint32)
+    np.bitwise_or.at(bits, ids >> 5, np.uint32(1) << (ids & 31).astype(np.uint32))
+    return bits
+
+
+def _favoured_ids(ids, N: int) -> np.ndarray:
+    """A favoured set as unique ascending int64 ids, refused outside [0, N)."""
+    a = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids).reshape(-1)
+    if a.size and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() >= N):
+        raise ValueError(f"layer-wise sampling: favoured nodes must be integer ids in [0, {N})")
+    return np.unique(a.astype(np.int64))
+
+
+def _scale_of(scale_factor) -> int:
+    """The skew's integer scale in [1, 64] (an integer-valued float passes)."""
+    f = float(scale_factor)
+    if f != int(f):
+        raise ValueError(f"layer-wise sampling: scale_factor {scale_factor} is not an integer; the device draw gives a "
+                         "favoured column `scale` replicas per entry, and a fractional weight has no exact integer "
+                         "race (the numpy branch of gnn_amd/sampler.py takes any factor)")
+    if not 1 <= int(f) <= MAX_SCALE:
+        raise ValueError(f"layer-wise sampling: scale_factor must lie in [1, {MAX_SCALE}], got {scale_factor}")
+    return int(f)
+
+
+def _favoured_layers(skewed_sampling_nodes, L: int, N: int) -> List[Optional[np.ndarray]]:
+    """Per model layer (0 = bottom) the favoured ids or None, from one id array (every layer) or a
+    list indexed by layer — ``placement.get_skewed_sampled_nodes``'s, which the reference reads as
+    ``skewed_sampling_nodes[len(orders1) - d - 1]``."""
+    if skewed_sampling_nodes is None:
+        return [None] * L
+    if isinstance(skewed_sampling_nodes, (list, tuple)):
+        if len(skewed_sampling_nodes) != L:
+            raise ValueError(f"layer-wise sampling: {len(skewed_sampling_nodes)} favoured sets for {L} layers (one id "
+                             "array for every layer, or a list with one entry per layer, bottom-up)")
+        return [None if s is None else _favoured_ids(s, N) for s in skewed_sampling_nodes]
+    return [_favoured_ids(skewed_sampling_nodes, N)] * L
+
+
+def _check_skewed_rows(M: int, layer: int) -> None:
+    if M >= 1 << REPLICA_SHIFT:
+        raise ValueError(f"layer-wise sampling: layer {layer} has {M} rows; a skewed race needs fewer than "
+                         f"2^{REPLICA_SHIFT} (the row position shares the hashed word with the replica index)")
+
+
+def replica_max(seed: int, layer: int, i, c, s) -> np.ndarray:
+    """max over r < s of h_r(i, c) = mix64((c << 32 | r << 26 | i) + K) per entry (``s``: replicas per entry)."""
+    i, c, s = np.asarray(i).astype(np.uint64), np.asarray(c).astype(np.uint64), np.asarray(s)
+    h = entry_values(seed, layer, i, c)
+    K = race_key(seed, layer)
+    for r in range(1, int(s.max()) if s.size else 0):
+        m = s > r
+        with np.errstate(over="ignore"):
+            hr = mix64(((c[m] << np.uint64(32)) | np.uint64(r << REPLICA_SHIFT) | (i[m] & np.uint64(0xFFFFFFFF))) + K)
+        h[m] = np.maximum(h[m], hr)
+    return h
+
+
 def _column_max(N: int, i: np.ndarray, c: np.ndarray, h: np.ndarray):
     counts = np.bincount(c, minlength=N).astype(np.int64)
     keys = np.zeros(N, dtype=np.uint64)
@@ -80,12 +154,33 @@ def _column_max(N: int, i: np.ndarray, c: np.ndarray, h: np.ndarray):
     return counts, keys
 
 
-def race_keys(seed: int, layer: int, indptr, indices, rows):
+def _replicas(N: int, favoured: Optional[np.ndarray], scale: int) -> Optional[np.ndarray]:
+    """s(c) int64[N] of a skewed layer; None where nothing is favoured or the scale is 1."""
+    if favoured is None or favoured.size == 0 or scale == 1:
+        return None
+    s = np.ones(N, dtype=np.int64)
+    s[favoured] = scale
+    return s
+
+
+def _race(seed: int, layer: int, N: int, i: np.ndarray, c: np.ndarray, s: Optional[np.ndarray], M: int):
+    if s is None:
+        return _column_max(N, i, c, entry_values(seed, layer, i, c))
+    _check_skewed_rows(M, layer)
+    return _column_max(N, i, c, replica_max(seed, layer, i, c, s[c]))
+
+
+def race_keys(seed: int, layer: int, indptr, indices, rows, favoured=None, scale=1):
     """(counts int64[N], keys uint64[N]) of U = lap[rows, :]: the entries and the largest entry
-    value per column node (key 0 where the count is 0)."""
+    value per column node (key 0 where the count is 0). With ``favoured`` (node ids) and an
+    integer ``scale`` > 1 the keys are the skewed draw's, over every entry's replicas; the counts
+    stay the raw entry counts."""
     indptr, indices = np.asarray(indptr), np.asarray(indices)
-    i, c, _ = _entries(indptr, indices, np.asarray(rows, dtype=np.int64).reshape(-1))
-    return _column_max(indptr.size - 1, i, c, entry_values(seed, layer, i, c))
+    N = indptr.size - 1
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    i, c, _ = _entries(indptr, indices, rows)
+    s = _replicas(N, None if favoured is None else _favoured_ids(favoured, N), _scale_of(scale))
+    return _race(seed, layer, N, i, c, s, rows.size)
 
 
 def race_select(counts: np.ndarray, keys: np.ndarray, samp_num: int):
@@ -98,10 +193,13 @@ def race_select(counts: np.ndarray, keys: np.ndarray, samp_num: int):
     return s_num, np.sort(live[part]).astype(np.int64)
 
 
-def race_normfact(counts: np.ndarray, after: np.ndarray, s_num: int) -> np.ndarray:
+def race_normfact(counts: np.ndarray, after: np.ndarray, s_num: int, weights: Optional[np.ndarray] = None) -> np.ndarray:
     """sampler.py:137, float32: 1 / float32(clip(s_num * p[after], 1e-10, 1)) with p = counts /
     sum(counts) in float64 (the reciprocal is a float32 division; p counts as 0 when nothing was
-    counted, where the reference would have divided by zero)."""
+    counted, where the reference would have divided by zero). ``weights`` (int64[N], the skewed
+    draw's counts * s) take the counts' place."""
+    if weights is not None:
+        counts = weights
     total = int(counts.sum())
     p = counts[after] / total if total > 0 else np.zeros(after.size)
     return 1 / np.clip(s_num * p, 1e-10, 1).astype(np.float32)
@@ -139,16 +237,20 @@ def _graph_of(lap):
     return g
 
 
-def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequence[int]) -> HostLayerwiseBatch:
+def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequence[int], skewed_sampling_nodes=None,
+                     scale_factor=1) -> HostLayerwiseBatch:
     """The whole batch in numpy: per layer (bottom-up, as ``adjs``) the operand pieces (rowptr, col,
     val, shape) of adj = lap[rows, :][:, after] with create_coo_tensor's values, the positions of
     the rows in ``after`` and the layer-0 input nodes. ``samp_num_list``: one int, or the
     reference's list (one per layer, top-down); ``lap`` a scipy matrix or a sampler.NativeGraph
-    without stored values."""
+    without stored values. ``skewed_sampling_nodes`` (one id array, or a list indexed by layer with
+    None for no skew) and an integer ``scale_factor`` in [1, 64]: the locality-skewed draw."""
     g = _graph_of(lap)
     sl = _samp_list(samp_num_list, orders)
     L = len(sl)
     N = g.num_nodes
+    scale = _scale_of(scale_factor)
+    favoured = _favoured_layers(skewed_sampling_nodes, L, N)
     rows = _batch_ids(batch_nodes, N)
     layers, sampled, sets = [None] * L, [np.zeros(0, np.int64)] * L, [None] * (L + 1)
     s_nums, nfs = [None] * L, [None] * L
@@ -158,10 +260,11 @@ def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequenc
             sets[l] = rows
             continue
         i, c, deg = _entries(g.indptr, g.indices, rows)
-        counts, keys = _column_max(N, i, c, entry_values(seed, l, i, c))
+        s = _replicas(N, favoured[l], scale)
+        counts, keys = _race(seed, l, N, i, c, s, rows.size)
         s_num, selected = race_select(counts, keys, sl[l])
         after = np.unique(np.concatenate([selected, rows]))
-        nf = race_normfact(counts, after, s_num)
+        nf = race_normfact(counts, after, s_num, None if s is None else counts * s)
         K = int(after.size)
         pos = np.minimum(np.searchsorted(after, c), K - 1) if K else np.zeros(0, np.int64)
         keep = after[pos] == c if K else np.zeros(0, bool)
@@ -198,16 +301,38 @@ class LayerwiseSampler(ResidentSampler):
     the next layer's read, and of one last read per batch. With ``device="cpu"`` the same batches
     come from ``ladies_race_host`` as torch COO operands.
 
-    Out of scope, refused: weighted graphs, scale_factor > 1, FastGCN, subgraph sampling;
-    ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
+    ``scale_factor`` (an integer in [1, 64]; 2.0 passes) with ``skewed_sampling_nodes`` is the
+    locality-skewed draw: a favoured column's weight is its count times the scale. The favoured
+    sets are one id array, used at every aggregating layer, or a list indexed by the model's layer
+    index with None for no skew — ``placement.get_skewed_sampled_nodes(...)`` as it is; the bottom
+    layer's natural set over a placed store is ``PlacedFeatures.resident_nodes()``. Each layer's set
+    goes to the device once, as a bit table; ``sample`` hands it to gnn_lw_race_skew and
+    gnn_lw_finish_skew: the same launches, the same single read per layer.
 
-    def __init__(self, lap, samp_num, orders, feats: torch.Tensor, labels_full, device, scale_factor: float = 1.0):
-        if scale_factor > 1:
-            raise ValueError("LayerwiseSampler: scale_factor > 1 (locality-skewed weights) is out of scope of "
-                             "the device draw")
+    Out of scope, refused: weighted graphs, a non-integer scale_factor or one above 64, a skewed
+    layer of 2^26 rows or more, scale_factor > 1 with nothing to favour, FastGCN, subgraph
+    sampling; ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
+
+    def __init__(self, lap, samp_num, orders, feats: torch.Tensor, labels_full, device, scale_factor: float = 1.0,
+                 skewed_sampling_nodes=None):
+        self.scale = _scale_of(scale_factor)
+        if self.scale > 1 and skewed_sampling_nodes is None:
+            raise ValueError(f"LayerwiseSampler: scale_factor {scale_factor} without skewed_sampling_nodes: there is "
+                             "nothing to favour")
         self.graph = _graph_of(lap)
         self.samp_nums = _samp_list(samp_num, orders)
         self._setup(orders, feats, labels_full, device)
+        # per layer the favoured ids, or None where the draw is the plain one
+        self.favoured = [f if self.samp_nums[l] is not None and f is not None and f.size and self.scale > 1 else None
+                         for l, f in enumerate(_favoured_layers(skewed_sampling_nodes, len(self.orders), self.N))]
+        self._favoured_dev: list = [None] * len(self.orders)
+        if self.native:
+            made: dict = {}  # one id array for every layer is one table
+            for l, f in enumerate(self.favoured):
+                if f is not None:
+                    if id(f) not in made:
+                        made[id(f)] = torch.from_numpy(favoured_bits(f, self.N).view(np.int32)).to(self.device)
+                    self._favoured_dev[l] = made[id(f)]
         # a list here receives (layer, stage, event) after every stage of the device draw: the
         # per-kernel split of scripts/layerwise_probe.py (timing events; off by default)
         self.trace: Optional[list] = None
@@ -249,6 +374,10 @@ class LayerwiseSampler(ResidentSampler):
                 M = int(rows.numel())
                 if rowseg_total >= 2**31 or 2 * M + rowseg_total >= 2**31:
                     raise RuntimeError(f"LayerwiseSampler: layer {l} spans {rowseg_total} graph entries (>= 2^31)")
+                fav = self._favoured_dev[l]
+                if fav is not None:
+                    _check_skewed_rows(M, l)
+                fav_p = None if fav is None else fav.data_ptr()
                 cap = min(N, M + rowseg_total)     # >= the rows and their columns: the live table
                 kcap = min(N, M + min(cap, samp))  # >= |after|
                 # |live table|, sum(count), s_num, tau, K, nnz, colseg total, next rowseg total, (flag, the
@@ -278,9 +407,9 @@ class LayerwiseSampler(ResidentSampler):
                            "gnn_closure_mark")
                 _lib.check(Lb.gnn_closure_list(live.data_ptr(), N, p(live_ids), cap, st), "gnn_closure_list")
                 self._mark(l, "mark_live+list")
-                _lib.check(Lb.gnn_lw_race(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, E, p(rows), M,
-                                          live.data_ptr(), seed, l, p(count), p(key), cap, word[1:].data_ptr(),
-                                          err.data_ptr(), st), "gnn_lw_race")
+                _lib.check(Lb.gnn_lw_race_skew(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, E, p(rows), M,
+                                               live.data_ptr(), seed, l, p(count), p(key), cap, word[1:].data_ptr(),
+                                               err.data_ptr(), st, fav_p, self.scale), "gnn_lw_race_skew")
                 self._mark(l, "race")
                 _lib.check(Lb.gnn_lw_select(p(key), p(count), word[0:].data_ptr(), cap, samp, p(live_ids), p(ids),
                                             word[2:].data_ptr(), word[3:].data_ptr(), ws.data_ptr(), wsb, st),
@@ -290,11 +419,12 @@ class LayerwiseSampler(ResidentSampler):
                                                word[4:].data_ptr(), ws.data_ptr(), wsb, st), "gnn_closure_mark")
                 _lib.check(Lb.gnn_closure_list(table.data_ptr(), N, p(after), kcap, st), "gnn_closure_list")
                 self._mark(l, "mark_after+list")
-                _lib.check(Lb.gnn_lw_finish(dg.indptr.data_ptr(), E, dg.indptr_t.data_ptr(), Et, N, p(rows), M,
-                                            p(after), word[4:].data_ptr(), kcap, live.data_ptr(), p(count), cap,
-                                            word[1:].data_ptr(), word[2:].data_ptr(), p(normfact), colptr.data_ptr(),
-                                            rowseg.data_ptr(), colseg.data_ptr(), word[5:].data_ptr(), ws.data_ptr(),
-                                            wsb, err.data_ptr(), st), "gnn_lw_finish")
+                _lib.check(Lb.gnn_lw_finish_skew(dg.indptr.data_ptr(), E, dg.indptr_t.data_ptr(), Et, N, p(rows), M,
+                                                 p(after), word[4:].data_ptr(), kcap, live.data_ptr(), p(count), cap,
+                                                 word[1:].data_ptr(), word[2:].data_ptr(), p(normfact),
+                                                 colptr.data_ptr(), rowseg.data_ptr(), colseg.data_ptr(),
+                                                 word[5:].data_ptr(), ws.data_ptr(), wsb, err.data_ptr(), st, fav_p,
+                                                 self.scale), "gnn_lw_finish_skew")
                 self._mark(l, "finish")
                 err[1:2].copy_(dg.err)  # the extractions so far (the layer above's among them)
                 K, nnz, colseg_total, next_total, flags = (int(v) for v in word[4:].tolist())
@@ -320,7 +450,8 @@ class LayerwiseSampler(ResidentSampler):
         return NeighborBatch(x0, adjs, sampled, self._labels(q), input_nodes, q, seed)
 
     def _sample_cpu(self, q: np.ndarray, seed: int) -> NeighborBatch:
-        hb = ladies_race_host(seed, q, [s or 1 for s in self.samp_nums[::-1]], self.graph, self.orders)  # top-down
+        hb = ladies_race_host(seed, q, [s or 1 for s in self.samp_nums[::-1]], self.graph, self.orders,  # top-down
+                              self.favoured, self.scale)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
         adjs = []
         for lay in hb.layers:

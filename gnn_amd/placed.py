@@ -310,6 +310,19 @@ class PlacedFeatures:
                                                         _lib.stream_of(dev)), "gnn_gather_placed_f32")
         return out
 
+    def resident_nodes(self, which: str = "own") -> np.ndarray:
+        """Node ids (int64, ascending) the map serves without the host link: ``"own"`` those of source
+        0, this rank's buffer (what the reference's subgraph sampler skews by); ``"device"`` those of any
+        source, the union of the buffers. The bottom layer's favoured set of a locality-skewed draw
+        (``layerwise.LayerwiseSampler(..., skewed_sampling_nodes=...)``)."""
+        if which not in ("own", "device"):
+            raise ValueError(f"PlacedFeatures.resident_nodes: which is 'own' or 'device', got {which!r}")
+        place = self._place_host
+        on = place != PLACE_HOST
+        if which == "own":
+            on &= ((place.astype(np.int64) & 0xFFFFFFFF) >> PLACE_SHIFT) == 0
+        return np.flatnonzero(on).astype(np.int64)
+
     # ------------------------------------------------------------------ counters and the flag
     def _read(self) -> np.ndarray:
         return self._words.cpu().numpy() if self.native else np.concatenate([self._total, [self._bad]])

@@ -232,15 +232,48 @@ int gnn_nbr_relabel(const void* table, int64_t num_nodes, const int32_t* ids, in
  *   total reads 2^31 - 1, so the outputs stay safe to read. workspace:
  *   gnn_lw_finish_workspace_bytes(M, kcap).
  *
+ * The locality-skewed draw (gnn_lw_race_skew, gnn_lw_finish_skew; the reference's sampler.py:119-121
+ * with preprocess.get_skewed_sampled_nodes: pi of a column that is cheap to fetch is multiplied by
+ * scale_factor before the draw, and normfact comes from the skewed p, so the estimator stays
+ * LADIES's). Inputs: scale, an integer in [1, 64], and the layer's favoured set F, a subset of
+ * [0, num_nodes), as a bit table favoured uint32[ceil(num_nodes / 32)] (device, 4-byte aligned):
+ * node c is bit c & 31 of word c >> 5.
+ *   s(c) = scale if c is in F, else 1. The entry of U in row position i and column c has s(c)
+ *   replicas; replica r (0 <= r < s(c)) has the value
+ *     h_r(i, c) = mix64((c << 32 | r << 26 | i) + K),   K as above; h_0 = h.
+ *   This needs i < 2^26: a skewed race over M >= 2^26 rows is refused. c < 2^31, r < 2^6 and
+ *   i < 2^26 occupy disjoint bit fields, so (c, r, i) is unique per replica, and mix64 being a
+ *   bijection all replica values, hence all column keys, are distinct: still no tie rule.
+ *   key[c] = max over i and r of h_r(i, c): the maximum of w[c] = count[c] * s(c) independent
+ *   uniform values, so the race is successive sampling without replacement proportional to w,
+ *   the law of np.random.choice(p = pi * scale / sum, replace = False).
+ *   count[c] stays the raw entry count (colptr_t, the operand's nnz and gnn_ladies_extract_f32's
+ *   cross-check read it as such); *total = sum of w[c] (int64), w formed in 64 bits;
+ *   normfact[k] = 1.0f / (float)clip((double)s_num * ((double)w[after[k]] / (double)total),
+ *                                    1e-10, 1.0)
+ *   (sampler.py:137 on the scaled pi; for integer scales every intermediate is exact in fp64).
+ *   With F empty, favoured == NULL or scale == 1 this is the plain draw bit for bit, and
+ *   gnn_lw_race / gnn_lw_finish are the skewed entry points called with (NULL, 1). Only integer
+ *   scales: a fractional weight has no exact integer race. gnn_lw_select is the same for both:
+ *   its liveness rule is count > 0 and keys are distinct.
+ *   race_skew: per entry, after the live table's lookup, one 4-byte read of the favoured word; the
+ *   replicas' maximum is taken in registers, so an entry still issues one 32-bit add and one
+ *   64-bit max; a wave adds the sum of s(c) to *total. finish_skew: the same scans, normfact's
+ *   weight alone becomes count * s(after[k]).
+ *
  * Memory safety does not depend on the contents of the device arrays: a row id outside
  * [0, num_nodes), a row pointer outside [0, num_entries] or running backwards, a column that is not
  * in the live table or sits at a position >= cap contribute nothing; *ntab and *K are clamped to
- * cap and kcap. Each case ORs 1 into err_flag (device int32, optional).
+ * cap and kcap. Each case ORs 1 into err_flag (device int32, optional). The skewed draw adds no
+ * case: the favoured word's index derives from a column that has passed the live table's lookup,
+ * so 0 <= c < num_nodes and the word lies inside the table whatever the arrays hold.
  *
  * Conventions as above: device pointers, stream-ordered, no allocation, no host synchronisation.
  * Refused with GNN_EINVAL before anything is launched: a negative size, a size >= 2^31,
  * samp_num < 1, a negative layer, a NULL pointer where one is read or written, a misaligned table
- * or 8-byte word, a workspace that is NULL, too small or not 16-byte aligned. */
+ * or 8-byte word, a workspace that is NULL, too small or not 16-byte aligned; of the skewed entry
+ * points also scale outside [1, 64], a favoured table that is not 4-byte aligned, and scale > 1
+ * with a table and M >= 2^26. */
 int gnn_lw_race(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
                 const int32_t* rows, int64_t M, const void* live_table, uint64_t seed, int32_t layer, int32_t* count,
                 uint64_t* key, int64_t cap, int64_t* total, int32_t* err_flag, void* stream);
@@ -254,6 +287,16 @@ int gnn_lw_finish(const int64_t* indptr, int64_t num_entries, const int64_t* ind
                   int64_t kcap, const void* live_table, const int32_t* count, int64_t cap, const int64_t* total,
                   const int64_t* s_num, float* normfact, int32_t* colptr_t, int32_t* rowseg, int32_t* colseg,
                   int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream);
+int gnn_lw_race_skew(const int64_t* indptr, const int32_t* indices, int64_t num_nodes, int64_t num_entries,
+                     const int32_t* rows, int64_t M, const void* live_table, uint64_t seed, int32_t layer,
+                     int32_t* count, uint64_t* key, int64_t cap, int64_t* total, int32_t* err_flag, void* stream,
+                     const uint32_t* favoured, int32_t scale);
+int gnn_lw_finish_skew(const int64_t* indptr, int64_t num_entries, const int64_t* indptr_t, int64_t num_entries_t,
+                       int64_t num_nodes, const int32_t* rows, int64_t M, const int32_t* after, const int64_t* K,
+                       int64_t kcap, const void* live_table, const int32_t* count, int64_t cap, const int64_t* total,
+                       const int64_t* s_num, float* normfact, int32_t* colptr_t, int32_t* rowseg, int32_t* colseg,
+                       int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream,
+                       const uint32_t* favoured, int32_t scale);
 
 #ifdef __cplusplus
 }
