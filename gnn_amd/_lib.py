@@ -68,6 +68,9 @@ _SIGNATURES = {
                                 _VP, _VP, _VP, _VP, ctypes.c_int32]),
     "gnn_lw_finish_skew": (_INT, [_VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP,
                                   _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP, _VP, ctypes.c_int32]),
+    "gnn_sg_count": (_INT, [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "gnn_sg_finish_workspace_bytes": (_SZ, [_I64]),
+    "gnn_sg_finish": (_INT, [_VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
     "gnn_spmm_set_timing_events": (None, [_VP, _VP]),
     "gnn_segsort_workspace_bytes": (_SZ, [_I64]),
     "gnn_build_operand_workspace_bytes": (_SZ, []),

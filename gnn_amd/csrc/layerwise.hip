@@ -28,6 +28,12 @@
 //   gnn_lw_finish  lw_chunk_scan (blockIdx.y = which scan; closure.hip's cl_chunk_scan shape; also
 //                  normfact and the exact 64-bit totals), scan_exclusive over the chunk sums of each
 //                  scan, lw_chunk_add (offsets, the closing entries, the totals and their clamp).
+// The subgraph sampler's square operand S = lap[after, :][:, after] (gnn_sg_*) needs two things more:
+//   gnn_sg_count   sg_count: a wave per member of after, grid-stride, lap^T's row of that node over
+//                  the lanes; each lane tests its entry against after's table and the wave sums the
+//                  ballots' popcounts: S's column counts without an atomic, whatever the schedule.
+//   gnn_sg_finish  the same three scan launches over two other sources (the column counts, and
+//                  deg(after) with its offsets this time).
 // The locality-skewed draw (gnn_lw_race_skew / gnn_lw_finish_skew: a favoured bit table and an integer
 // scale) gives an entry of a favoured column `scale` replicas; the race takes their maximum in
 // registers after one 4-byte read of the column's favoured word, and finish weighs normfact by
@@ -65,6 +71,11 @@ constexpr int LW_PASSES = 8;
 constexpr int LW_SEL_ITEMS = 8;            // keys per thread a select workgroup is sized for
 constexpr int LW_SEL_GRID = 1024;          // at most this many select workgroups
 constexpr int LW_SCANS = 3;                // colptr_t, rowseg, colseg (a fourth sum has no offsets)
+constexpr int SG_SCANS = 2;                // the square operand's colptr_t and rowseg
+
+// What a slot (blockIdx.y) of the chunk scans sums: count[after[k]] through the live table (and
+// normfact), deg(rows[i]), lap^T's row length of after[k], deg(after[k]), colcnt[k] as it stands.
+enum ScanSrc : int { SRC_COUNT = 0, SRC_DEG_ROWS = 1, SRC_DEGT_AFTER = 2, SRC_DEG_AFTER = 3, SRC_COLCNT = 4 };
 
 __host__ __device__ __forceinline__ u64 mix64(u64 z) {  // the splitmix64 finaliser
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -244,26 +255,31 @@ struct FinishArgs {
   const i64* total;
   const i64* s_num;
   float* normfact;
-  int32_t* out[LW_SCANS];  // colptr_t, rowseg, colseg
-  int32_t* csum;           // [LW_SCANS][cstride]
-  int32_t* coff;           // [LW_SCANS][cstride]
+  const int32_t* colcnt;   // SRC_COLCNT's values (gnn_sg_finish)
+  int src[LW_SCANS + 1];   // per slot, a ScanSrc
+  int nscan;               // slots below it have offsets (out[slot]); the others only a sum
+  int32_t* out[LW_SCANS];  // gnn_lw_finish: colptr_t, rowseg, colseg
+  int32_t* csum;           // [nscan][cstride]
+  int32_t* coff;           // [nscan][cstride]
   int cstride, nch;
-  i64* tot;                // [4]: the sums of the three scans and of deg(after), exact
-  int64_t* totals;         // the caller's (nnz, colseg total, deg(after) total)
+  i64* tot;                // [4]: the slots' sums, exact
+  int64_t* totals;         // the caller's totals: totals[j] = tot[totmap[j]], j < ntot, clamped
+  int ntot, totmap[3];
   int32_t* err;
   const uint32_t* favoured;  // the skewed draw's bit table, or NULL: every weight is the count
   int scale;
 };
 
-// blockIdx.y = which: 0 count[after[k]] (and normfact), 1 deg(rows[i]), 2 lap^T's row length of
-// after[k], 3 deg(after[k]) (its sum only). Offsets within the chunk go to out[which], the chunk's
-// sum to csum (32-bit, wrapping; the exact sum goes to tot[which], which decides in lw_chunk_add).
+// blockIdx.y = which slot, a.src[which] what it sums (gnn_lw_finish: count[after[k]] and normfact,
+// deg(rows[i]), lap^T's row length of after[k], and deg(after[k]) as a sum only). Offsets within the
+// chunk go to out[which], the chunk's sum to csum (32-bit, wrapping; the exact sum goes to
+// tot[which], which decides in lw_chunk_add).
 __global__ __launch_bounds__(1024) void lw_chunk_scan_kernel(FinishArgs a) {
   __shared__ unsigned wsum[16];
-  const int which = blockIdx.y;
+  const int which = blockIdx.y, src = a.src[which];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t base = (int64_t)blockIdx.x * LW_CHUNK + (int64_t)tid * LW_ITEMS;
-  const int n = which == 1 ? a.M : (int)clamp_size(a.K, a.kcap);
+  const int n = src == SRC_DEG_ROWS ? a.M : (int)clamp_size(a.K, a.kcap);
   unsigned v[LW_ITEMS];
   unsigned tsum = 0;
   bool bad = false;
@@ -273,19 +289,22 @@ __global__ __launch_bounds__(1024) void lw_chunk_scan_kernel(FinishArgs a) {
     if (base + k < n) {
       int64_t b;
       int d = 0;
-      if (which == 0) {
+      if (src == SRC_COUNT) {
         const int p = table_pos(a.live, a.N, a.after[base + k]);
         d = (p >= 0 && p < a.cap) ? a.count[p] : 0;
         if (d < 0) d = 0;
         i64 w = d;  // p >= 0: after[base + k] lies in [0, N), inside the favoured table
         if (a.favoured && d > 0) w *= lw_replicas(a.favoured, a.scale, a.after[base + k]);
         a.normfact[base + k] = lw_normfact(w, *a.total, *a.s_num);
-      } else if (which == 1) {
+      } else if (src == SRC_DEG_ROWS) {
         bad |= !row_span(a.indptr, a.N, a.E, a.rows[base + k], b, d);
-      } else if (which == 2) {
+      } else if (src == SRC_DEGT_AFTER) {
         bad |= !row_span(a.indptr_t, a.N, a.E_t, a.after[base + k], b, d);
-      } else {
+      } else if (src == SRC_DEG_AFTER) {
         bad |= !row_span(a.indptr, a.N, a.E, a.after[base + k], b, d);
+      } else {
+        d = a.colcnt[base + k];
+        if (d < 0) d = 0;
       }
       v[k] = (unsigned)d;
     }
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(1024) void lw_chunk_scan_kernel(FinishArgs a) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) exact += __shfl_down(exact, d);
   if (lane == 0 && exact) (void)__hip_atomic_fetch_add(&a.tot[which], exact, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (which == LW_SCANS) return;  // block-uniform
+  if (which >= a.nscan) return;  // block-uniform
   unsigned x = tsum;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -328,11 +347,11 @@ __global__ __launch_bounds__(1024) void lw_chunk_scan_kernel(FinishArgs a) {
 }
 
 // offsets += the chunk's start; thread n writes the closing entry. A sum of 2^31 or more raises
-// the flag and leaves zero offsets; thread n of scan 0 also writes the caller's totals, clamped.
+// the flag and leaves zero offsets; thread n of slot 0 also writes the caller's totals, clamped.
 __global__ __launch_bounds__(256) void lw_chunk_add_kernel(FinishArgs a) {
   const int which = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int n = which == 1 ? a.M : (int)clamp_size(a.K, a.kcap);
+  const int n = a.src[which] == SRC_DEG_ROWS ? a.M : (int)clamp_size(a.K, a.kcap);
   if (i > n) return;
   const bool over = a.tot[which] > (i64)INT_MAX;
   int32_t* out = a.out[which];
@@ -344,14 +363,39 @@ __global__ __launch_bounds__(256) void lw_chunk_add_kernel(FinishArgs a) {
   out[n] = over ? 0 : coff[a.nch];
   bool flag = over;
   if (which == 0) {
-    const i64 t0 = a.tot[0], t2 = a.tot[2], t3 = a.tot[3];
-    a.totals[0] = t0 > INT_MAX ? INT_MAX : t0;
-    a.totals[1] = t2 > INT_MAX ? INT_MAX : t2;
-    a.totals[2] = t3 > INT_MAX ? INT_MAX : t3;
-    flag |= t3 > (i64)INT_MAX;
+    for (int j = 0; j < a.ntot; ++j) {
+      const i64 t = a.tot[a.totmap[j]];
+      a.totals[j] = t > INT_MAX ? INT_MAX : t;
+      flag |= t > (i64)INT_MAX;  // a sum-only slot has no thread of its own here
+    }
     flag |= *a.K != (int64_t)n;  // the set does not fit the caller's capacity
   }
   if (flag && a.err) atomicOr(a.err, 1);
+}
+
+// S's column counts: colcnt[k] = the entries of lap^T's row after[k] that are members of after's
+// table. A wave per k, grid-stride; the trip count is wave-uniform, so every ballot sees all lanes.
+__global__ __launch_bounds__(64 * LW_RACE_WAVES) void sg_count_kernel(
+    const int64_t* __restrict__ indptr_t, const int32_t* __restrict__ indices_t, int N, int64_t E_t,
+    const int32_t* __restrict__ after, const int64_t* __restrict__ K, int kcap, const Word* __restrict__ table,
+    int32_t* __restrict__ colcnt, int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * LW_RACE_WAVES + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * LW_RACE_WAVES;
+  const int64_t n = clamp_size(K, kcap);
+  bool bad = false;
+  for (int64_t k = wave; k < n; k += nwaves) {
+    int64_t b;
+    int d;
+    bad |= !row_span(indptr_t, N, E_t, after[k], b, d);
+    int cnt = 0;
+    for (int e = 0; e < d; e += 64) {  // d < 2^31 - 1: the sum fits
+      const bool member = e + lane < d && table_pos(table, N, indices_t[b + e + lane]) >= 0;
+      cnt += __popcll(__ballot(member));
+    }
+    if (lane == 0) colcnt[k] = cnt;
+  }
+  if (__ballot(bad) && lane == 0 && err) atomicOr(err, 1);
 }
 
 inline size_t csum_bytes(int64_t n) {
@@ -518,6 +562,10 @@ int gnn_lw_finish_skew(const int64_t* indptr, int64_t num_entries, const int64_t
   a.total = (const i64*)total;
   a.s_num = (const i64*)s_num;
   a.normfact = normfact;
+  a.colcnt = nullptr;
+  a.src[0] = SRC_COUNT, a.src[1] = SRC_DEG_ROWS, a.src[2] = SRC_DEGT_AFTER, a.src[3] = SRC_DEG_AFTER;
+  a.nscan = LW_SCANS;
+  a.ntot = 3, a.totmap[0] = 0, a.totmap[1] = 2, a.totmap[2] = 3;
   a.out[0] = colptr_t;
   a.out[1] = rowseg;
   a.out[2] = colseg;
@@ -540,6 +588,82 @@ int gnn_lw_finish_skew(const int64_t* indptr, int64_t num_entries, const int64_t
     if (rc) return rc;
   }
   lw_chunk_add_kernel<<<dim3((unsigned)ceil_div(n + 1, 256), LW_SCANS), dim3(256), 0, st>>>(a);
+  GNN_LAUNCHED("lw_chunk_add_kernel");
+  return 0;
+}
+
+int gnn_sg_count(const int64_t* indptr_t, const int32_t* indices_t, int64_t num_nodes, int64_t num_entries_t,
+                 const int32_t* after, const int64_t* K, int64_t kcap, const void* table, int32_t* colcnt,
+                 int32_t* err_flag, void* stream) {
+  GNN_REQUIRE(num_nodes >= 0 && num_entries_t >= 0 && kcap >= 0,
+              "gnn_sg_count: negative size (num_nodes, num_entries_t or kcap)");
+  GNN_REQUIRE(num_nodes < INT_MAX && kcap < INT_MAX, "gnn_sg_count: num_nodes and kcap must be < 2^31");
+  GNN_REQUIRE(K != nullptr, "gnn_sg_count: NULL K");
+  GNN_REQUIRE((uintptr_t)K % 8 == 0, "gnn_sg_count: K not 8-byte aligned");
+  GNN_REQUIRE(table != nullptr, "gnn_sg_count: NULL table");
+  GNN_REQUIRE((uintptr_t)table % 8 == 0, "gnn_sg_count: table not 8-byte aligned");
+  GNN_REQUIRE(kcap == 0 || (after && colcnt && indptr_t), "gnn_sg_count: NULL after/colcnt/indptr_t");
+  GNN_REQUIRE(kcap == 0 || num_entries_t == 0 || indices_t, "gnn_sg_count: NULL indices_t");
+  if (kcap == 0) return 0;
+  const int64_t g = ceil_div(kcap, (int64_t)LW_RACE_WAVES);
+  sg_count_kernel<<<dim3((unsigned)(g < LW_RACE_GRID ? g : LW_RACE_GRID)), dim3(64 * LW_RACE_WAVES), 0,
+                    (hipStream_t)stream>>>(indptr_t, indices_t, (int)num_nodes, num_entries_t, after, K, (int)kcap,
+                                           (const Word*)table, colcnt, err_flag);
+  GNN_LAUNCHED("sg_count_kernel");
+  return 0;
+}
+
+size_t gnn_sg_finish_workspace_bytes(int64_t kcap) {
+  return 2 * SG_SCANS * csum_bytes(kcap > 0 ? kcap : 0) + 256;  // the chunk sums, their scans, the exact totals
+}
+
+int gnn_sg_finish(const int64_t* indptr, int64_t num_entries, int64_t num_nodes, const int32_t* after,
+                  const int64_t* K, int64_t kcap, const int32_t* colcnt, int32_t* colptr_t, int32_t* rowseg,
+                  int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  GNN_REQUIRE(num_nodes >= 0 && num_entries >= 0 && kcap >= 0,
+              "gnn_sg_finish: negative size (num_nodes, num_entries or kcap)");
+  GNN_REQUIRE(num_nodes < INT_MAX && kcap < INT_MAX, "gnn_sg_finish: num_nodes and kcap must be < 2^31");
+  GNN_REQUIRE(K && totals, "gnn_sg_finish: NULL K/totals");
+  GNN_REQUIRE((uintptr_t)K % 8 == 0 && (uintptr_t)totals % 8 == 0, "gnn_sg_finish: K/totals not 8-byte aligned");
+  GNN_REQUIRE(colptr_t && rowseg, "gnn_sg_finish: NULL colptr_t/rowseg");
+  GNN_REQUIRE(kcap == 0 || (after && colcnt && indptr), "gnn_sg_finish: NULL after/colcnt/indptr");
+  const size_t need = gnn_sg_finish_workspace_bytes(kcap);
+  GNN_REQUIRE(workspace && workspace_bytes >= need, "gnn_sg_finish: workspace too small (%zu < %zu)",
+              workspace ? workspace_bytes : (size_t)0, need);
+  GNN_REQUIRE((uintptr_t)workspace % 16 == 0, "gnn_sg_finish: workspace not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int nch = (int)ceil_div(kcap, (int64_t)LW_CHUNK);
+  const size_t cb = csum_bytes(kcap);
+  FinishArgs a = {};
+  a.indptr = indptr;
+  a.E = num_entries;
+  a.N = (int)num_nodes;
+  a.after = after;
+  a.K = K;
+  a.kcap = (int)kcap;
+  a.colcnt = colcnt;
+  a.src[0] = SRC_COLCNT, a.src[1] = SRC_DEG_AFTER;
+  a.nscan = SG_SCANS;
+  a.ntot = 2, a.totmap[0] = 0, a.totmap[1] = 1;
+  a.out[0] = colptr_t;
+  a.out[1] = rowseg;
+  a.csum = (int32_t*)workspace;
+  a.coff = (int32_t*)((char*)workspace + SG_SCANS * cb);
+  a.cstride = (int)(cb / sizeof(int32_t));
+  a.nch = nch;
+  a.tot = (i64*)((char*)workspace + 2 * SG_SCANS * cb);
+  a.totals = totals;
+  a.err = err_flag;
+  GNN_HIP(hipMemsetAsync(a.tot, 0, 4 * sizeof(i64), st), "hipMemsetAsync");
+  if (nch > 0) {
+    lw_chunk_scan_kernel<<<dim3((unsigned)nch, SG_SCANS), dim3(1024), 0, st>>>(a);
+    GNN_LAUNCHED("lw_chunk_scan_kernel");
+  }
+  for (int w = 0; w < SG_SCANS; ++w) {
+    int rc = gnn::launch_scan_exclusive(a.csum + w * a.cstride, nch, a.coff + w * a.cstride, st);
+    if (rc) return rc;
+  }
+  lw_chunk_add_kernel<<<dim3((unsigned)ceil_div(kcap + 1, 256), SG_SCANS), dim3(256), 0, st>>>(a);
   GNN_LAUNCHED("lw_chunk_add_kernel");
   return 0;
 }

@@ -31,6 +31,7 @@ scale 1, every array is the plain draw's bit for bit.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -237,6 +238,19 @@ def _graph_of(lap):
     return g
 
 
+def _operand_of(i: np.ndarray, c: np.ndarray, deg: np.ndarray, after: np.ndarray, nf: np.ndarray):
+    """(rowptr, col, val, shape) of adj = lap[rows, :][:, after] from ``_entries``' (i, c, deg) of the
+    rows: create_coo_tensor's values, (float)((1.0 / deg(row)) * (double)normfact[col])."""
+    M, K = int(deg.size), int(after.size)
+    pos = np.minimum(np.searchsorted(after, c), K - 1) if K else np.zeros(0, np.int64)
+    keep = after[pos] == c if K else np.zeros(0, bool)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(i[keep], minlength=M))]).astype(np.int32)
+    col = pos[keep].astype(np.int32)
+    with np.errstate(divide="ignore"):
+        val = ((1.0 / deg.astype(np.float64))[i[keep]] * nf.astype(np.float64)[col]).astype(np.float32)
+    return rowptr, col, val, (M, K)
+
+
 def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequence[int], skewed_sampling_nodes=None,
                      scale_factor=1) -> HostLayerwiseBatch:
     """The whole batch in numpy: per layer (bottom-up, as ``adjs``) the operand pieces (rowptr, col,
@@ -265,21 +279,138 @@ def ladies_race_host(seed: int, batch_nodes, samp_num_list, lap, orders: Sequenc
         s_num, selected = race_select(counts, keys, sl[l])
         after = np.unique(np.concatenate([selected, rows]))
         nf = race_normfact(counts, after, s_num, None if s is None else counts * s)
-        K = int(after.size)
-        pos = np.minimum(np.searchsorted(after, c), K - 1) if K else np.zeros(0, np.int64)
-        keep = after[pos] == c if K else np.zeros(0, bool)
-        rowptr = np.concatenate([[0], np.cumsum(np.bincount(i[keep], minlength=rows.size))]).astype(np.int32)
-        col = pos[keep].astype(np.int32)
-        with np.errstate(divide="ignore"):
-            val = ((1.0 / deg.astype(np.float64))[i[keep]] * nf.astype(np.float64)[col]).astype(np.float32)
-        layers[l] = (rowptr, col, val, (int(rows.size), K))
+        layers[l] = _operand_of(i, c, deg, after, nf)
         sampled[l] = np.searchsorted(after, rows).astype(np.int64)
         s_nums[l], nfs[l] = s_num, nf
         sets[l] = rows = after
     return HostLayerwiseBatch(layers, sampled, sets[0], sets, s_nums, nfs)
 
 
-class LayerwiseSampler(ResidentSampler):
+class RaceSampler(ResidentSampler):
+    """What the samplers that draw by the race share (``LayerwiseSampler`` here,
+    ``subgraph.SubgraphSampler``): a layer's launches from the first mark to gnn_lw_finish_skew, its one
+    device-to-host read, the favoured sets' bit tables, the timing trace and the ``device="cpu"``
+    batch."""
+
+    # a list here receives (layer, stage, event) after every stage of the device draw: the
+    # per-kernel split of scripts/layerwise_probe.py (timing events; off by default)
+    trace: Optional[list] = None
+
+    def _mark(self, layer: int, stage: str) -> None:
+        if self.trace is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.trace.append((layer, stage, ev))
+
+    def _favoured_table(self, f: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(favoured_bits(f, self.N).view(np.int32)).to(self.device)
+
+    def _draw(self, rows: torch.Tensor, rowseg_total: int, seed: int, l: int, samp: int,
+              fav: Optional[torch.Tensor], extra_words: int = 0, extra_ws: int = 0) -> SimpleNamespace:
+        """The draw of layer ``l`` over ``rows`` (int32, on the device) under ``seed``, launched on the
+        current stream and not read: mark(expand), list, race, select, mark(rows ++ ids), list, finish. Returns the
+        buffers, sized by the host-known bounds ``cap`` and ``kcap``; ``word`` (int64[9 + extra_words])
+        holds |live table|, sum(count), s_num, tau, K, nnz, colseg total, sum of deg(after), (flag,
+        the extractions' flag) and the caller's extra words, ``err`` is word 8 as int32[2]; the
+        workspace has at least ``extra_ws`` bytes."""
+        from . import _lib
+
+        who = type(self).__name__
+        dev, N, dg = self.device, self.N, self.dgraph
+        Lb = _lib.lib()
+        st = _lib.stream_of(dev)
+        E, Et = int(dg.indices.numel()), int(dg.indices_t.numel())
+        p = lambda t: t.data_ptr() if t.numel() else None
+        M = int(rows.numel())
+        if rowseg_total >= 2**31 or 2 * M + rowseg_total >= 2**31:
+            raise RuntimeError(f"{who}: layer {l} spans {rowseg_total} graph entries (>= 2^31)")
+        if fav is not None:
+            _check_skewed_rows(M, l)
+        fav_p = None if fav is None else fav.data_ptr()
+        cap = min(N, M + rowseg_total)     # >= the rows and their columns: the live table
+        kcap = min(N, M + min(cap, samp))  # >= |after|
+        # words 4 .. 8 (and the extra ones) are the layer's one device-to-host read
+        word = torch.zeros(9 + extra_words, dtype=torch.int64, device=dev)
+        err = word[8:9].view(torch.int32)
+        wsb = max(Lb.gnn_closure_workspace_bytes(N), Lb.gnn_lw_select_workspace_bytes(),
+                  Lb.gnn_lw_finish_workspace_bytes(M, kcap), extra_ws)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        tbytes = Lb.gnn_closure_table_bytes(N)
+        live = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+        table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+        live_ids = torch.empty(cap, dtype=torch.int32, device=dev)
+        count = torch.empty(cap, dtype=torch.int32, device=dev)
+        key = torch.empty(cap, dtype=torch.int64, device=dev)
+        seeds = torch.empty(M + cap, dtype=torch.int32, device=dev)  # rows ++ selected ids (or -1)
+        seeds[:M] = rows
+        ids = seeds[M:]
+        after = torch.empty(kcap, dtype=torch.int32, device=dev)
+        normfact = torch.empty(kcap, dtype=torch.float32, device=dev)
+        colptr = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
+        colseg = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
+        rowseg = torch.empty(M + 1, dtype=torch.int32, device=dev)
+        self._mark(l, "begin")
+        _lib.check(Lb.gnn_closure_mark(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, p(rows), M, 1,
+                                       live.data_ptr(), word[0:].data_ptr(), ws.data_ptr(), wsb, st),
+                   "gnn_closure_mark")
+        _lib.check(Lb.gnn_closure_list(live.data_ptr(), N, p(live_ids), cap, st), "gnn_closure_list")
+        self._mark(l, "mark_live+list")
+        _lib.check(Lb.gnn_lw_race_skew(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, E, p(rows), M,
+                                       live.data_ptr(), seed, l, p(count), p(key), cap, word[1:].data_ptr(),
+                                       err.data_ptr(), st, fav_p, self.scale), "gnn_lw_race_skew")
+        self._mark(l, "race")
+        _lib.check(Lb.gnn_lw_select(p(key), p(count), word[0:].data_ptr(), cap, samp, p(live_ids), p(ids),
+                                    word[2:].data_ptr(), word[3:].data_ptr(), ws.data_ptr(), wsb, st),
+                   "gnn_lw_select")
+        self._mark(l, "select")
+        _lib.check(Lb.gnn_closure_mark(None, None, N, p(seeds), M + cap, 0, table.data_ptr(),
+                                       word[4:].data_ptr(), ws.data_ptr(), wsb, st), "gnn_closure_mark")
+        _lib.check(Lb.gnn_closure_list(table.data_ptr(), N, p(after), kcap, st), "gnn_closure_list")
+        self._mark(l, "mark_after+list")
+        _lib.check(Lb.gnn_lw_finish_skew(dg.indptr.data_ptr(), E, dg.indptr_t.data_ptr(), Et, N, p(rows), M,
+                                         p(after), word[4:].data_ptr(), kcap, live.data_ptr(), p(count), cap,
+                                         word[1:].data_ptr(), word[2:].data_ptr(), p(normfact),
+                                         colptr.data_ptr(), rowseg.data_ptr(), colseg.data_ptr(),
+                                         word[5:].data_ptr(), ws.data_ptr(), wsb, err.data_ptr(), st, fav_p,
+                                         self.scale), "gnn_lw_finish_skew")
+        self._mark(l, "finish")
+        return SimpleNamespace(word=word, err=err, ws=ws, wsb=wsb, cap=cap, kcap=kcap, table=table, after=after,
+                               normfact=normfact, colptr=colptr, colseg=colseg, rowseg=rowseg)
+
+    def _read(self, d: SimpleNamespace, l: int) -> List[int]:
+        """The one device-to-host read of a draw: word 4 on — K, nnz, the colseg total, the sum of
+        deg(after), then the caller's extra words — after the flags, which raise."""
+        d.err[1:2].copy_(self.dgraph.err)  # the extractions so far (the layer above's among them)
+        K, nnz, colseg_total, next_total, flags, *extra = (int(v) for v in d.word[4:].tolist())
+        if flags & 0xFFFFFFFF:
+            raise RuntimeError(f"{type(self).__name__}: the device draw of layer {l} met a row or column outside "
+                               "the graph or a total >= 2^31 (the resident graph does not match its row pointer)")
+        if flags >> 32:
+            self.dgraph.check()
+        return [K, nnz, colseg_total, next_total] + extra
+
+    def _host_batch(self, hb: HostLayerwiseBatch, q: np.ndarray, seed: int) -> NeighborBatch:
+        """A numpy batch as torch COO operands on the host (layers that share their pieces share the
+        operand)."""
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+        adjs, made = [], {}
+        for lay in hb.layers:
+            if lay is None:
+                adjs.append(None)
+                continue
+            if id(lay) not in made:
+                rowptr, col, val, (M, K) = lay
+                r = np.repeat(np.arange(M, dtype=np.int64), np.diff(rowptr))
+                # create_coo_tensor's CPU branch: the same values, coalesced
+                made[id(lay)] = torch.sparse_coo_tensor(torch.stack([t(r), t(col.astype(np.int64))]), t(val),
+                                                        (M, K)).coalesce()
+            adjs.append(made[id(lay)])
+        idx = t(hb.input_nodes.astype(np.int64))
+        x0 = self._x0_host(idx)
+        return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)
+
+
+class LayerwiseSampler(RaceSampler):
     """LADIES batches of ``lap`` for a model with layer ``orders`` (0 / 1, bottom-up), drawn by the
     race over the resident graph.
 
@@ -310,8 +441,9 @@ class LayerwiseSampler(ResidentSampler):
     gnn_lw_finish_skew: the same launches, the same single read per layer.
 
     Out of scope, refused: weighted graphs, a non-integer scale_factor or one above 64, a skewed
-    layer of 2^26 rows or more, scale_factor > 1 with nothing to favour, FastGCN, subgraph
-    sampling; ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw."""
+    layer of 2^26 rows or more, scale_factor > 1 with nothing to favour, FastGCN;
+    ``NativeLoader`` / ``Stager`` / ``bench.py`` keep the host draw. The subgraph sampler (one draw,
+    one square operand for every layer below it) is ``subgraph.SubgraphSampler``."""
 
     def __init__(self, lap, samp_num, orders, feats: torch.Tensor, labels_full, device, scale_factor: float = 1.0,
                  skewed_sampling_nodes=None):
@@ -331,17 +463,8 @@ class LayerwiseSampler(ResidentSampler):
             for l, f in enumerate(self.favoured):
                 if f is not None:
                     if id(f) not in made:
-                        made[id(f)] = torch.from_numpy(favoured_bits(f, self.N).view(np.int32)).to(self.device)
+                        made[id(f)] = self._favoured_table(f)
                     self._favoured_dev[l] = made[id(f)]
-        # a list here receives (layer, stage, event) after every stage of the device draw: the
-        # per-kernel split of scripts/layerwise_probe.py (timing events; off by default)
-        self.trace: Optional[list] = None
-
-    def _mark(self, layer: int, stage: str) -> None:
-        if self.trace is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.trace.append((layer, stage, ev))
 
     def sample(self, batch_nodes, seed: int) -> NeighborBatch:
         """The batch of ``batch_nodes`` (integer node ids, any order) under the draw seed ``seed``."""
@@ -352,93 +475,30 @@ class LayerwiseSampler(ResidentSampler):
         from . import _lib
 
         dev, N, dg = self.device, self.N, self.dgraph
-        Lb = _lib.lib()
         nl = len(self.orders)
         adjs: list = [None] * nl
         sampled: list = [None] * nl
         unique_top = np.unique(q).size == q.size
         hp = dg.host_indptr
         with _lib.on_device(dev):
-            st = _lib.stream_of(dev)
-            E, Et = int(dg.indices.numel()), int(dg.indices_t.numel())
             rows = torch.from_numpy(q.astype(np.int32)).to(dev)
             rowseg_total = int((hp[q + 1] - hp[q]).sum())  # the top layer's: host data
             empty = torch.zeros(0, dtype=torch.int64, device=dev)
             top = True
-            p = lambda t: t.data_ptr() if t.numel() else None
             for l in range(nl - 1, -1, -1):
                 samp = self.samp_nums[l]
                 if samp is None:
                     sampled[l] = empty
                     continue
                 M = int(rows.numel())
-                if rowseg_total >= 2**31 or 2 * M + rowseg_total >= 2**31:
-                    raise RuntimeError(f"LayerwiseSampler: layer {l} spans {rowseg_total} graph entries (>= 2^31)")
-                fav = self._favoured_dev[l]
-                if fav is not None:
-                    _check_skewed_rows(M, l)
-                fav_p = None if fav is None else fav.data_ptr()
-                cap = min(N, M + rowseg_total)     # >= the rows and their columns: the live table
-                kcap = min(N, M + min(cap, samp))  # >= |after|
-                # |live table|, sum(count), s_num, tau, K, nnz, colseg total, next rowseg total, (flag, the
-                # extractions' flag): words 4 .. 8 are the layer's one device-to-host read
-                word = torch.zeros(9, dtype=torch.int64, device=dev)
-                err = word[8:].view(torch.int32)
-                wsb = max(Lb.gnn_closure_workspace_bytes(N), Lb.gnn_lw_select_workspace_bytes(),
-                          Lb.gnn_lw_finish_workspace_bytes(M, kcap))
-                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                tbytes = Lb.gnn_closure_table_bytes(N)
-                live = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-                table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-                live_ids = torch.empty(cap, dtype=torch.int32, device=dev)
-                count = torch.empty(cap, dtype=torch.int32, device=dev)
-                key = torch.empty(cap, dtype=torch.int64, device=dev)
-                seeds = torch.empty(M + cap, dtype=torch.int32, device=dev)  # rows ++ selected ids (or -1)
-                seeds[:M] = rows
-                ids = seeds[M:]
-                after = torch.empty(kcap, dtype=torch.int32, device=dev)
-                normfact = torch.empty(kcap, dtype=torch.float32, device=dev)
-                colptr = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
-                colseg = torch.empty(kcap + 1, dtype=torch.int32, device=dev)
-                rowseg = torch.empty(M + 1, dtype=torch.int32, device=dev)
-                self._mark(l, "begin")
-                _lib.check(Lb.gnn_closure_mark(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, p(rows), M, 1,
-                                               live.data_ptr(), word[0:].data_ptr(), ws.data_ptr(), wsb, st),
-                           "gnn_closure_mark")
-                _lib.check(Lb.gnn_closure_list(live.data_ptr(), N, p(live_ids), cap, st), "gnn_closure_list")
-                self._mark(l, "mark_live+list")
-                _lib.check(Lb.gnn_lw_race_skew(dg.indptr.data_ptr(), dg.indices.data_ptr(), N, E, p(rows), M,
-                                               live.data_ptr(), seed, l, p(count), p(key), cap, word[1:].data_ptr(),
-                                               err.data_ptr(), st, fav_p, self.scale), "gnn_lw_race_skew")
-                self._mark(l, "race")
-                _lib.check(Lb.gnn_lw_select(p(key), p(count), word[0:].data_ptr(), cap, samp, p(live_ids), p(ids),
-                                            word[2:].data_ptr(), word[3:].data_ptr(), ws.data_ptr(), wsb, st),
-                           "gnn_lw_select")
-                self._mark(l, "select")
-                _lib.check(Lb.gnn_closure_mark(None, None, N, p(seeds), M + cap, 0, table.data_ptr(),
-                                               word[4:].data_ptr(), ws.data_ptr(), wsb, st), "gnn_closure_mark")
-                _lib.check(Lb.gnn_closure_list(table.data_ptr(), N, p(after), kcap, st), "gnn_closure_list")
-                self._mark(l, "mark_after+list")
-                _lib.check(Lb.gnn_lw_finish_skew(dg.indptr.data_ptr(), E, dg.indptr_t.data_ptr(), Et, N, p(rows), M,
-                                                 p(after), word[4:].data_ptr(), kcap, live.data_ptr(), p(count), cap,
-                                                 word[1:].data_ptr(), word[2:].data_ptr(), p(normfact),
-                                                 colptr.data_ptr(), rowseg.data_ptr(), colseg.data_ptr(),
-                                                 word[5:].data_ptr(), ws.data_ptr(), wsb, err.data_ptr(), st, fav_p,
-                                                 self.scale), "gnn_lw_finish_skew")
-                self._mark(l, "finish")
-                err[1:2].copy_(dg.err)  # the extractions so far (the layer above's among them)
-                K, nnz, colseg_total, next_total, flags = (int(v) for v in word[4:].tolist())
-                if flags & 0xFFFFFFFF:
-                    raise RuntimeError(f"LayerwiseSampler: the device draw of layer {l} met a row or column outside "
-                                       "the graph or a total >= 2^31 (the resident graph does not match its row pointer)")
-                if flags >> 32:
-                    dg.check()
-                after = after[:K]
+                d = self._draw(rows, rowseg_total, seed, l, samp, self._favoured_dev[l])
+                K, nnz, colseg_total, next_total = self._read(d, l)
+                after = d.after[:K]
                 tr = l >= 1 and not top  # unique ascending rows: the extraction builds the transpose as well
-                op = cso.extract_operand(dg, rows, after, normfact[:K], nnz, rowseg,
-                                         colseg[: K + 1] if tr else None, colptr[: K + 1] if tr else None,
+                op = cso.extract_operand(dg, rows, after, d.normfact[:K], nnz, d.rowseg,
+                                         d.colseg[: K + 1] if tr else None, d.colptr[: K + 1] if tr else None,
                                          rowseg_total=rowseg_total, colseg_total=colseg_total if tr else None)
-                sn = cso.closure_rank(table, N, rows)
+                sn = cso.closure_rank(d.table, N, rows)
                 if l >= 1:  # the top layer's transpose is made here; below it is in place already
                     self._top_maps(op, sn, M, K, unique_top or not top)
                 adjs[l], sampled[l] = op, sn
@@ -452,16 +512,4 @@ class LayerwiseSampler(ResidentSampler):
     def _sample_cpu(self, q: np.ndarray, seed: int) -> NeighborBatch:
         hb = ladies_race_host(seed, q, [s or 1 for s in self.samp_nums[::-1]], self.graph, self.orders,  # top-down
                               self.favoured, self.scale)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
-        adjs = []
-        for lay in hb.layers:
-            if lay is None:
-                adjs.append(None)
-                continue
-            rowptr, col, val, (M, K) = lay
-            r = np.repeat(np.arange(M, dtype=np.int64), np.diff(rowptr))
-            # create_coo_tensor's CPU branch: the same values, coalesced
-            adjs.append(torch.sparse_coo_tensor(torch.stack([t(r), t(col.astype(np.int64))]), t(val), (M, K)).coalesce())
-        idx = t(hb.input_nodes.astype(np.int64))
-        x0 = self._x0_host(idx)
-        return NeighborBatch(x0, adjs, [t(s) for s in hb.sampled_nodes], self._labels(q), idx, q, seed)
+        return self._host_batch(hb, q, seed)

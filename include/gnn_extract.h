@@ -298,6 +298,55 @@ int gnn_lw_finish_skew(const int64_t* indptr, int64_t num_entries, const int64_t
                        int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream,
                        const uint32_t* favoured, int32_t scale);
 
+/* The subgraph sampler's batch on the device (the reference's sampler.py:7-88): ONE draw over the
+ * batch rows, then every layer below the drawn one aggregates over the same induced square operand.
+ *
+ * The law. orders[l] in {0, 1}, bottom-up; t = the topmost layer with orders[t] = 1; rows = the batch
+ * nodes (M of them, any order, repeats allowed).
+ *   The draw is the race above over U = lap[rows, :] with layer = t: the same K, h, h_r, count, key
+ *   and select, samp_num = the reference's samp_num_list[0] (sampler.py:28), and optionally one
+ *   favoured set with an integer scale in [1, 64] (the reference's own set is the nodes placed on the
+ *   drawing device, sampler.py:23-25).
+ *   after = unique(selected ++ rows), K of them; normfact as gnn_lw_finish_skew writes it
+ *   (sampler.py:40).
+ *   Layer t: adj = lap[rows, :][:, after] with gnn_ladies_extract_f32's values and sampled_nodes = the
+ *   positions of rows in after — for the same (rows, seed, samp_num) bit for bit the top layer of the
+ *   layer-wise draw.
+ *   Every layer l < t with orders[l] = 1: the square operand S = lap[after, :][:, after] (K x K),
+ *   S's value at (i, col) = (float)((1.0 / deg(after[i])) * (double)normfact[col]) with the same
+ *   normfact array (sampler.py:62), sampled_nodes = 0 .. K-1. S is built once per batch.
+ *   An order-0 layer has no operand. The input nodes are after.
+ *
+ * S by gnn_ladies_extract_f32(rows = cols = after) needs, beyond gnn_lw_finish's colseg (the scan of
+ * lap^T's row lengths of after), S's nnz, its row segments and the row pointer of its transpose:
+ * count: for k < *K (device int64, clamped to kcap) colcnt[k] = the number of entries of lap^T's row
+ *   after[k] (indptr_t / indices_t, which may alias lap's when the structure is symmetric) that are
+ *   members of table, the gnn_closure_mark table of after: the entry count of S's column k. Taken
+ *   over lap^T the count needs no atomic and does not depend on the schedule: a wave per k,
+ *   grid-stride, the row's entries over the lanes, the wave sums the popcounts of its ballots and
+ *   lane 0 stores. Nothing is written at or past min(*K, kcap).
+ * finish: colptr_t int32[K+1] = the exclusive scan of colcnt (closing entry: S's nnz), rowseg
+ *   int32[K+1] = the exclusive scan of deg(after[k]) over lap, totals int64[2] (device) = S's nnz and
+ *   rowseg[K]. gnn_lw_finish's chunked scans and its overflow rule: a sum of 2^31 or more ORs 1 into
+ *   err_flag, its offsets are then all zero and its total reads 2^31 - 1. *K above kcap is clamped
+ *   and flagged. workspace: gnn_sg_finish_workspace_bytes(kcap), 16-byte aligned.
+ *
+ * Memory safety does not depend on the contents of the device arrays: a member of after outside
+ * [0, num_nodes), or a row pointer outside [0, num_entries] or running backwards, counts 0 and ORs 1
+ * into err_flag (device int32, optional); an entry of lap^T outside [0, num_nodes) is no member.
+ *
+ * Conventions as above: device pointers, stream-ordered, no allocation, no host synchronisation.
+ * Refused with GNN_EINVAL before anything is launched: a negative size, a size >= 2^31, a NULL
+ * pointer where one is read or written, a misaligned table or 8-byte word, a workspace that is
+ * NULL, too small or not 16-byte aligned. */
+int gnn_sg_count(const int64_t* indptr_t, const int32_t* indices_t, int64_t num_nodes, int64_t num_entries_t,
+                 const int32_t* after, const int64_t* K, int64_t kcap, const void* table, int32_t* colcnt,
+                 int32_t* err_flag, void* stream);
+size_t gnn_sg_finish_workspace_bytes(int64_t kcap);
+int gnn_sg_finish(const int64_t* indptr, int64_t num_entries, int64_t num_nodes, const int32_t* after,
+                  const int64_t* K, int64_t kcap, const int32_t* colcnt, int32_t* colptr_t, int32_t* rowseg,
+                  int64_t* totals, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
